@@ -33,6 +33,13 @@ Secondary workloads (``--workload``; same JSON schema, reported in DESIGN.md, no
 
 Launch: ``python bench.py`` (N=1) or
 ``python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N``.
+
+A plain run of the default workload sets up, warms up, times ``--steps`` steps and prints the result
+line (the roofline of the main pass comes from the timed steps themselves).  ``--full`` adds the
+measurements that take runs of their own: the streaming-skeleton ceiling, the two-stream record and
+the CPU baseline at N = 1, the nested sharded records at N > 1.  ``--dump-outputs DIR`` writes what
+the last timed step returned as ``DIR/<name>.npy`` (inputs are seeded: two builds can be compared
+output for output).
 """
 import argparse
 import datetime
@@ -64,13 +71,20 @@ def parse():
     ap.add_argument("--ratio", type=float, default=0.01)
     ap.add_argument("--numel", type=int, default=64 * 1024 * 1024)
     ap.add_argument("--buffers", type=int, default=3, help="distinct buckets rotated (defeats MALL reuse)")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: also run the measurements beside the headline (streaming-skeleton "
+                         "ceiling, two-stream record, CPU baseline; at N > 1 the nested sharded records)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step as DIR/<name>.npy (a fixed seeded sample and the "
+                         "non-zero entries where the result is larger than the size limit)")
     ap.add_argument("--cpu-baseline-steps", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full, skip the CPU baseline")
     ap.add_argument("--stream", choices=["default", "side"], default="default",
                     help="issue the workload on torch's default stream or on one created stream")
-    ap.add_argument("--no-overlap", action="store_true", help="skip the two-stream record of the top-k workload")
+    ap.add_argument("--no-overlap", action="store_true", help="with --full, skip the two-stream record of the top-k workload")
     ap.add_argument("--no-sharded", action="store_true",
-                    help="at N > 1, skip the nested sharded (configs[4]) measurement of the default workload")
+                    help="with --full at N > 1, skip the nested sharded (configs[4]) measurement of the default "
+                         "workload")
     return ap.parse_args()
 
 
@@ -89,7 +103,54 @@ def resnet50_shapes():
     return shapes
 
 
+DUMP_DIR = None                # --dump-outputs: set by main(), cleared by the first timed() (the headline's)
+DUMP_BUDGET = 48 << 20         # bytes of array data written per run
+
+
+def dump_outputs(dirname, result):
+    """Write the tensors of one step's result (a tensor, or tensors nested in tuples / lists) as
+    ``<dirname>/<name>.npy``: float64 and 32- / 64-bit integer tensors as float64, the others as float32.
+    A tensor within its share of DUMP_BUDGET is written whole (``output``, or ``output0``, ... for
+    several).  Of a larger one: ``<name>_sample`` at the sorted positions ``<name>_sample_index``
+    (drawn once from a fixed seed), and, where they fit, all non-zero entries as
+    ``<name>_nonzero_index`` / ``<name>_nonzero_value`` (a sparse codec's dense result in full)."""
+    import numpy as np
+    tensors = []
+
+    def walk(x):
+        if torch.is_tensor(x):
+            tensors.append(x)
+        elif isinstance(x, (tuple, list)):
+            for y in x:
+                walk(y)
+
+    walk(result)
+    os.makedirs(dirname, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
+
+    for i, t in enumerate(tensors):
+        name = "output" if len(tensors) == 1 else f"output{i}"
+        flat = t.detach().reshape(-1)
+        flat = flat.to(torch.float64 if flat.dtype in (torch.float64, torch.int32, torch.int64) else torch.float32)
+        item = flat.element_size()
+        share = DUMP_BUDGET // len(tensors)
+        if flat.numel() * item <= share:
+            save(name, flat)
+            continue
+        m = share // (2 * (item + 8))           # entries of the sample, and the most non-zeros written
+        idx = torch.randint(0, flat.numel(), (m,), generator=torch.Generator().manual_seed(0)).sort().values
+        save(name + "_sample_index", idx.to(torch.float64))
+        save(name + "_sample", flat[idx.to(flat.device)])
+        nz = torch.nonzero(flat).reshape(-1)
+        if nz.numel() <= m:
+            save(name + "_nonzero_index", nz.to(torch.float64))
+            save(name + "_nonzero_value", flat[nz])
+
+
 def timed(fn, steps, warmup, world, dev):
+    global DUMP_DIR
     for i in range(warmup):
         fn(i)
     torch.cuda.synchronize()
@@ -97,8 +158,12 @@ def timed(fn, steps, warmup, world, dev):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for i in range(steps):
-        fn(warmup + i)
+        if i + 1 < steps:
+            fn(warmup + i)
+        else:                   # only the last result is held: an engine reuses a result once it is dropped
+            last = fn(warmup + i)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -106,6 +171,11 @@ def timed(fn, steps, warmup, world, dev):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if DUMP_DIR is not None:
+        if world == 1 or dist.get_rank() == 0:
+            dump_outputs(DUMP_DIR, last)
+        DUMP_DIR = None
+    del last
     return elapsed
 
 
@@ -122,6 +192,9 @@ def main():
         local_rank = 0
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
+    torch.manual_seed(1234 + rank)      # the same inputs from run to run (--dump-outputs compares builds)
+    global DUMP_DIR
+    DUMP_DIR = args.dump_outputs
     if world > 1:
         backend = os.environ.get("GRACE_BENCH_BACKEND", "nccl")
         # a bounded collective timeout: a rank that never arrives ends the job instead of holding
@@ -141,7 +214,7 @@ def main():
             line = run(args, world, rank, dev)
     else:
         line = run(args, world, rank, dev)
-    if args.workload == "topk" and world > 1 and not args.no_sharded:
+    if args.workload == "topk" and world > 1 and args.full and not args.no_sharded:
         # BASELINE configs[4] (one 256 MiB bucket sharded over the ranks, top-k 0.1 %) rides in the
         # same JSON line, so the driver's 1 -> 8 GPU record covers it next to the DP replicas
         line["sharded"] = nested_sharded(line, args, world, rank, dev)
@@ -381,8 +454,8 @@ def bench_topk(args, world, rank, dev):
     # the fraction against a bandwidth measured on this box as well -- the main
     # pass's own streaming skeleton (same kernel, chunking, loads and stores, no classification),
     # each launch right after a real step, timed like the main pass
-    skel, skel_med = (skeleton_ceiling(step, main_bytes, n, dev, sparse=recycled) if not NO_PROBE and world == 1
-                      else (None, None))
+    skel, skel_med = (skeleton_ceiling(step, main_bytes, n, dev, sparse=recycled)
+                      if args.full and not NO_PROBE and world == 1 else (None, None))
     roofline["measured_copy_gbs"] = skel
     roofline["measured_copy_median_gbs"] = skel_med
     roofline["measured_copy_kind"] = ("grace_topk_stream_probe: the topk_main kernel itself with the classification "
@@ -395,10 +468,10 @@ def bench_topk(args, world, rank, dev):
     roofline["frac_of_measured_copy_median"] = round(achieved / skel_med, 4) if skel_med else None
     line["roofline"] = roofline
     line["clocks"] = clocks
-    if world == 1 and not args.no_overlap:
+    if args.full and world == 1 and not args.no_overlap:
         line["two_streams"] = bench_topk_two_streams(args, grads, names)
     line["cpu_baseline"] = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_baseline_steps > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_baseline_steps > 0:
         line["cpu_baseline"] = cpu_baseline_topk(n, args.ratio, args.cpu_baseline_steps)
     return line
 
@@ -636,6 +709,7 @@ def bench_topk_e2e(args, world, rank, dev):
         dbuf.copy_(hosts[i % 2], non_blocking=True)
         out = comm.step(dbuf, "bucket")
         back.copy_(out, non_blocking=True)
+        return back
 
     step(0)
     elapsed = timed(step, args.steps, args.warmup, world, dev)

@@ -73,10 +73,38 @@ class Store:
             self.arrays[f"{case}__{k}"] = np_(v)
 
     def save(self):
-        path = os.path.join(OUT, f"{self.name}.npz")
-        np.savez_compressed(path, **self.arrays)
+        sizes = save_parts(OUT, self.name, self.arrays)
         MANIFEST[self.name] = self.cases
-        print(f"{self.name}: {len(self.cases)} cases, {os.path.getsize(path)} bytes")
+        print(f"{self.name}: {len(self.cases)} cases, {len(sizes)} part(s), {sum(sizes)} bytes")
+
+
+PART_BYTES = 960 << 10   # every committed fixture file stays below 1 MiB
+
+
+def save_parts(outdir, name, arrays):
+    """Write ``arrays`` as ``<name>.npz`` where they fit one file, otherwise as ``<name>.000.npz``,
+    ``<name>.001.npz``, ...: keys in insertion order, a new part wherever the next array would take
+    the part past PART_BYTES (raw bytes plus 512 per entry for the zip and npy headers; compression
+    only shrinks it).  The loader (tests/golden_util.py) merges the parts.  Returns the file sizes."""
+    for old in os.listdir(outdir):
+        if old.startswith(name + ".") and old.endswith(".npz"):
+            os.remove(os.path.join(outdir, old))
+    parts, cur, used = [], {}, 0
+    for k, v in arrays.items():
+        need = v.nbytes + 512
+        if cur and used + need > PART_BYTES:
+            parts.append(cur)
+            cur, used = {}, 0
+        cur[k] = v
+        used += need
+    parts.append(cur)
+    sizes = []
+    for i, part in enumerate(parts):
+        path = os.path.join(outdir, f"{name}.{i:03d}.npz" if len(parts) > 1 else f"{name}.npz")
+        np.savez_compressed(path, **part)
+        sizes.append(os.path.getsize(path))
+        assert sizes[-1] < (1 << 20), path
+    return sizes
 
 
 def init_world1():

@@ -3,6 +3,7 @@
 The fixtures were produced by tests/golden/gen_golden.py from the reference
 implementation; this module only reads data (numpy.load, allow_pickle=False).
 """
+import glob
 import json
 import os
 
@@ -28,8 +29,14 @@ class Golden:
 
     def _npz(self, family):
         if family not in self._files:
-            with np.load(os.path.join(GOLDEN_DIR, family + ".npz"), allow_pickle=False) as z:
-                self._files[family] = {k: z[k] for k in z.files}
+            # a large family is stored in parts (<family>.000.npz, ...) so that no file reaches 1 MiB
+            parts = (sorted(glob.glob(os.path.join(GOLDEN_DIR, family + ".[0-9][0-9][0-9].npz")))
+                     or [os.path.join(GOLDEN_DIR, family + ".npz")])
+            arrs = {}
+            for path in parts:
+                with np.load(path, allow_pickle=False) as z:
+                    arrs.update({k: z[k] for k in z.files})
+            self._files[family] = arrs
         return self._files[family]
 
     def cases(self, family, codec=None, prefix=None):

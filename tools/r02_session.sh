@@ -12,7 +12,7 @@ for step in ${STEPS:-pytest smoke bench secondary prof}; do
   case $step in
     pytest) run pytest_gpu 900 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread ;;
     smoke) run smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 300 python3 bench.py ;;
+    bench) run bench 300 python3 bench.py --full ;;
     secondary)
       : > gpurun_out/secondary.jsonl
       for wl in ${WL:-sign sign256 qsgd terngrad powersgd topk_sharded topk_e2e ddp_params ddp_segmented ddp_bucket}; do

@@ -13,7 +13,7 @@ for step in ${STEPS:-pytest smoke bench}; do
     pytest) run pytest_gpu 1100 python3 -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;;
     pyfiles) run pytest_files 1100 python3 -u -m pytest ${FILES} -x -v --timeout 120 --timeout-method thread ;;
     smoke) run smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 300 python3 bench.py ;;
+    bench) run bench 300 python3 bench.py --full ;;
     secondary)
       : > gpurun_out/secondary.jsonl
       for wl in ${WL:-sign sign256 qsgd terngrad powersgd}; do

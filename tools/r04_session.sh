@@ -13,7 +13,7 @@ for step in ${STEPS:-pytest smoke bench}; do
     pytest) run pytest_gpu 1100 python3 -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;;
     pyfiles) run pytest_files 1100 python3 -u -m pytest ${FILES} -x -v --timeout 120 --timeout-method thread ;;
     smoke) run smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 300 python3 bench.py ;;
+    bench) run bench 300 python3 bench.py --full ;;
     secondary)
       : > gpurun_out/secondary.jsonl
       for wl in ${WL:-sign sign256 qsgd terngrad powersgd}; do
@@ -43,7 +43,7 @@ for step in ${STEPS:-pytest smoke bench}; do
               for inj in none all 1; do
                 run w2_$inj 240 env GRACE_BENCH_INJECT_SHARDED_FAILURE=$inj GRACE_BENCH_SHARDED_LIMIT=60 \
                   GRACE_BENCH_ONE_DEVICE=1 GRACE_BENCH_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 \
-                  --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29521 bench.py --gpus 2 --steps 5 --warmup 2
+                  --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29521 bench.py --gpus 2 --full --steps 5 --warmup 2
                 grep '^{' gpurun_out/w2_$inj.log | tail -1
               done ;;
   esac

@@ -47,7 +47,7 @@ for s in "$@"; do
       run sq_head_kt 120 rocprofv3 --kernel-trace --stats --output-format csv -d $O/sq_head_kt -o run \
           -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-overlap
       python3 tools/pmc_sq_summary.py $O/sq_head > $O/sq_head_summary.json; echo "sq summary rc=$?" ;;
-    bench) run bench 300 python3 bench.py ;;
+    bench) run bench 300 python3 bench.py --full ;;
     prof) # the headline, single stream, no in-bench probes (tools/prof_steady.py keeps the timed launches)
           GRACE_BENCH_NO_PROBE=1 run prof_topk 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_topk -o run \
             -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-overlap

@@ -43,7 +43,7 @@ for s in "$@"; do
     prof) GRACE_BENCH_NO_PROBE=1 run prof_topk 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_topk -o run \
             -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-overlap
           python3 tools/prof_steady.py $O/prof_topk --last 20 --out $O/prof_topk_steady.json; echo "steady rc=$?" ;;
-    bench) run bench 300 python3 bench.py ;;
+    bench) run bench 300 python3 bench.py --full ;;
     secondary)
       : > $O/secondary.jsonl
       for wl in ${WL:-topk_nomem topk_sharded ddp_segmented sign sign256 qsgd qsgd_step terngrad terngrad_step powersgd randomk threshold dgc natural cnat fp16 sign_bits}; do

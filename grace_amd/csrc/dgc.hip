@@ -980,9 +980,6 @@ grace_status_t grace_dgc_step_w1_fused(const float* g, const float* residual, co
   GRACE_CHECK_LAUNCH("grace_dgc_step_w1_fused");
   // gated fix-up (returns at once unless thr0 did not stand): the reference's full adjustment loop,
   // on grids small enough that the no-op launches cost little
-#ifdef GRACE_DGC_NO_FIXUP   // diagnostic A/B build only: what the five no-op launches cost (wrong when a fix is due)
-  return GRACE_OK;
-#endif
   dgc_table_kernel<true><<<1, 1024, 0, s>>>(top_vals, ks, w);   // the adjustment table, zeroed counts
   GRACE_CHECK_LAUNCH("grace_dgc_step_w1_fused");
   const unsigned sg = stream_grid((n + 3) / 4, kDBlock * kDQ, 1024);

@@ -92,15 +92,6 @@ struct AccOp {
   __device__ void one(int64_t i) const { acc[i] = (first ? 0.f : acc[i]) + x[i]; }
 };
 
-struct FillOp {
-  float v; float* o;
-  __device__ void vec(int64_t i) const {   // write-only stream: non-temporal 16-B stores
-    typedef float f4v __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store(f4v{v, v, v, v}, reinterpret_cast<f4v*>(o) + i);
-  }
-  __device__ void one(int64_t i) const { o[i] = v; }
-};
-
 __device__ __forceinline__ uint32_t pack_ge0(float4 x) {
   return (uint32_t)(x.x >= 0.f) | ((uint32_t)(x.y >= 0.f) << 8) | ((uint32_t)(x.z >= 0.f) << 16) |
          ((uint32_t)(x.w >= 0.f) << 24);
@@ -194,13 +185,7 @@ struct SignStepOp {
 // World-1 sign step without codes (the launch-bound 4 MiB configs[0] step): U float4 per thread,
 // every load issued before any store (one HBM latency per thread), no grid-stride loop; the scalar
 // tail (n % 4) is handled by the first workgroup.
-#ifndef GRACE_SIGN_NT
-#define GRACE_SIGN_NT 0
-#endif
-#ifndef GRACE_SIGN_BLOCK
-#define GRACE_SIGN_BLOCK 256
-#endif
-constexpr int kSignBlock = GRACE_SIGN_BLOCK;
+constexpr int kSignBlock = 256;
 typedef float sf4v __attribute__((ext_vector_type(4)));
 template <int U>
 __global__ __launch_bounds__(kSignBlock) void sign_step_w1_kernel(const float* __restrict__ x, float* __restrict__ o,
@@ -212,8 +197,7 @@ __global__ __launch_bounds__(kSignBlock) void sign_step_w1_kernel(const float* _
   for (int u = 0; u < U; ++u) {
     const int64_t i = base + (int64_t)u * kSignBlock;
     const sf4v* src = reinterpret_cast<const sf4v*>(x) + (i < n4 ? i : 0);
-    if constexpr (GRACE_SIGN_NT & 1) v[u] = __builtin_nontemporal_load(src);
-    else v[u] = *src;
+    v[u] = *src;
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -221,8 +205,7 @@ __global__ __launch_bounds__(kSignBlock) void sign_step_w1_kernel(const float* _
     if (i < n4) {
       const sf4v r = {v[u].x >= 0.f ? 1.f : -1.f, v[u].y >= 0.f ? 1.f : -1.f, v[u].z >= 0.f ? 1.f : -1.f,
                       v[u].w >= 0.f ? 1.f : -1.f};
-      if constexpr (GRACE_SIGN_NT & 2) __builtin_nontemporal_store(r, reinterpret_cast<sf4v*>(o) + i);
-      else reinterpret_cast<sf4v*>(o)[i] = r;
+      reinterpret_cast<sf4v*>(o)[i] = r;
     }
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
@@ -480,19 +463,13 @@ grace_status_t grace_hbm_probe(float* r, const float* g, float* o, int64_t n, in
 // A fill is the runtime's 32-bit memset: it writes 256 MiB at 6.1 TB/s on MI355X against 4.6 TB/s for
 // a grid-stride float4 kernel and 5.4 TB/s for one 16 KiB tile per workgroup (tools/write_probe.hip,
 // profiles/r05_write_probe.txt) -- bit-identical, the word is the float's bits.
-#ifndef GRACE_FILL_MEMSET
-#define GRACE_FILL_MEMSET 1
-#endif
 grace_status_t grace_fill(float* x, float value, int64_t n, void* stream) {
   GRACE_REQUIRE(n >= 0 && x, "grace_fill: bad arguments");
-  if (GRACE_FILL_MEMSET) {
-    if (n == 0) return GRACE_OK;
-    const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(x), (int)__builtin_bit_cast(uint32_t, value),
-                                           (size_t)n, as_stream(stream));
-    if (e != hipSuccess) { set_error("grace_fill", e); return GRACE_ERR_HIP; }
-    return GRACE_OK;
-  }
-  return launch_stream("grace_fill", FillOp{value, x}, n, aligned16(x), stream);
+  if (n == 0) return GRACE_OK;
+  const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(x), (int)__builtin_bit_cast(uint32_t, value),
+                                         (size_t)n, as_stream(stream));
+  if (e != hipSuccess) { set_error("grace_fill", e); return GRACE_ERR_HIP; }
+  return GRACE_OK;
 }
 
 grace_status_t grace_accumulate(float* acc, const float* x, int64_t n, int32_t first, void* stream) {
@@ -531,10 +508,7 @@ grace_status_t grace_signum_encode(const float* g, float* momentum, int32_t has_
 grace_status_t grace_sign_step_w1(const float* x, uint8_t* codes, float* out, int64_t n, void* stream) {
   GRACE_REQUIRE(n >= 0 && x && out, "grace_sign_step_w1: bad arguments");
   if (!codes && n >= 4 && aligned16(x) && aligned16(out)) {
-#ifndef GRACE_SIGN_U
-#define GRACE_SIGN_U 1   // A/B over 200 steps: U = 1, 2 -> 5.1 us/step, U = 4 -> 5.7, U = 8 -> 5.5
-#endif
-    constexpr int U = GRACE_SIGN_U;
+    constexpr int U = 1;   // A/B over 200 steps: U = 1, 2 -> 5.1 us/step, U = 4 -> 5.7, U = 8 -> 5.5
     const int64_t grid = ((n >> 2) + kSignBlock * U - 1) / (kSignBlock * U);
     sign_step_w1_kernel<U><<<(unsigned)grid, kSignBlock, 0, as_stream(stream)>>>(x, out, n);
     GRACE_CHECK_LAUNCH("grace_sign_step_w1");

@@ -19,25 +19,16 @@ namespace grace {
 
 constexpr int kPChunkLog = 13;
 constexpr int kPChunk = 1 << kPChunkLog;
-#ifndef GRACE_P_BLOCK
-#define GRACE_P_BLOCK 256
-#endif
-// decode workgroup (A/B knob; 8 x 671 K entries into 256 MiB, tools/exp_wn_local.py: 256 threads
+// decode workgroup (A/B; 8 x 671 K entries into 256 MiB, tools/exp_wn_local.py: 256 threads
 // 58 us, 512 68 us, 1024 146 us)
-constexpr int kPBlock = GRACE_P_BLOCK;
+constexpr int kPBlock = 256;
 
-#ifndef GRACE_GROUP_BLOCK
-#define GRACE_GROUP_BLOCK 1024
-#endif
-#ifndef GRACE_GROUP_PER
-#define GRACE_GROUP_PER 4
-#endif
 // 4096 entries per workgroup over 1024 threads: the per-workgroup clear and scan of the 8192-bin
 // LDS histogram (one bin per output chunk) dominate a pass, so they are spread over as many threads
 // as possible (A/B, 671,088 entries: 256 x 16 -> 37.4 us, 512 x 8 -> 29.7, 1024 x 4 -> 27.6,
 // 1024 x 8 -> 35.3, 256 x 64 -> 64.1)
-constexpr int kGroupBlock = GRACE_GROUP_BLOCK;
-constexpr int kGroupPer = GRACE_GROUP_PER;             // entries per thread
+constexpr int kGroupBlock = 1024;
+constexpr int kGroupPer = 4;                           // entries per thread
 constexpr int kMaxGroupChunks = 32768;                 // LDS histogram bins (128 KB): n <= 2^28
 
 // pass 1: per-workgroup LDS histogram of chunk ids, flushed with one device atomic per non-zero bin
@@ -322,10 +313,7 @@ grace_status_t grace_sparse_aggregate_sorted(const float* vals, const uint16_t* 
                     (n + kPChunk - 1) / kPChunk <= kMaxGroupChunks,
                 "grace_sparse_aggregate_sorted: bad arguments (1 <= world <= 1024, n <= 2^28)");
   const int64_t nchunks = (n + kPChunk - 1) / kPChunk;
-#ifndef GRACE_DEC_SMALLW
-#define GRACE_DEC_SMALLW 1
-#endif
-  if (GRACE_DEC_SMALLW && world <= kWave)
+  if (world <= kWave)
     chunk_accumulate_kernel<true><<<(unsigned)nchunks, kPBlock, 0, as_stream(stream)>>>(
         vals, off, reinterpret_cast<const int32_t*>(ends), stride, world, divisor, out, n);
   else

@@ -60,16 +60,7 @@ __device__ __forceinline__ float sum_partials(const float* __restrict__ p, int64
   return t;
 }
 
-#ifdef GRACE_KFAN
-constexpr int kFan = GRACE_KFAN;
-#else
 constexpr int kFan = 8;                     // slabs per first-level reduction group
-#endif
-#ifdef GRACE_PS_OCC
-#define PS_OCC __attribute__((amdgpu_waves_per_eu(GRACE_PS_OCC, 8)))
-#else
-#define PS_OCC
-#endif
 
 // t[i] = sum over k < cnt (in order) of p[k * stride + f0 + threadIdx.x + i * 256], i < 4, for
 // entries below `nent`; 4 x 8 loads in flight per round
@@ -159,11 +150,7 @@ __device__ __forceinline__ float normal_at(uint64_t seed, uint64_t i) {
 constexpr int kTileR = 16;
 constexpr int kPW = 4;                      // waves per workgroup (both kernels)
 constexpr int kPBlockT = kPW * kWave;
-#ifdef GRACE_TILE_CPL
-constexpr int kCPL = GRACE_TILE_CPL;        // columns per lane / 4 of the streamed tiles
-#else
-constexpr int kCPL = 1;
-#endif
+constexpr int kCPL = 1;                     // columns per lane / 4 of the streamed tiles
 template <int CPL> struct Tile {
   static constexpr int C = 256 * CPL;       // tile columns
   static constexpr int LD = C + 4;          // padded LDS row
@@ -284,7 +271,7 @@ constexpr int kPPer = kTileR * kMaxRank / kPBlockT;   // 1: P rows of one row ti
 // DRAWQ: q is not read but drawn on the fly (standard normal, counter-based, keyed by `seed`; the
 // same values grace_normal_fill writes), so PowerSGD's fresh q needs no buffer and no launch.
 template <bool VEC, bool R4, bool DRAWQ = false>
-__global__ __launch_bounds__(kPBlockT) PS_OCC void psgd_p_kernel(const float* __restrict__ M, int64_t n, int64_t m,
+__global__ __launch_bounds__(kPBlockT) void psgd_p_kernel(const float* __restrict__ M, int64_t n, int64_t m,
                                                          const float* __restrict__ q, int r,
                                                          float* __restrict__ P, float* __restrict__ part,
                                                          uint32_t* __restrict__ tickets, uint64_t seed = 0) {
@@ -477,7 +464,7 @@ __device__ __forceinline__ void qt_reduce_slabs(const float* stg, int64_t m, int
 // next tile's (M rows and their P rows).  The slabs are reduced in two fixed-order levels (groups
 // of kFan slabs, then the groups), each by the last workgroup to arrive.
 template <bool VEC>
-__global__ __launch_bounds__(kPBlockT) PS_OCC void psgd_qt_kernel(const float* __restrict__ M, int64_t n, int64_t m,
+__global__ __launch_bounds__(kPBlockT) void psgd_qt_kernel(const float* __restrict__ M, int64_t n, int64_t m,
                                                           const float* __restrict__ P, int r, int64_t slab,
                                                           float* __restrict__ Q, float* __restrict__ part,
                                                           uint32_t* __restrict__ tickets) {
@@ -603,10 +590,6 @@ __global__ __launch_bounds__(kQ4Block) void psgd_qt4_kernel(const float* __restr
     }
     __syncthreads();
   }
-#ifdef GRACE_QT4_NORED   // diagnostic A/B build only: no slab reduction (wrong Q)
-  if (blockIdx.y == 0) for (int f = threadIdx.x; f < kQ4C * 4 && j0 * 4 + f < m * 4; f += kQ4Block) Q[j0 * 4 + f] = stg[f];
-  return;
-#endif
   qt_reduce_slabs<kQ4C, kQ4Block>(stg, m, 4, j0, cg, Q, part, tickets);
 }
 
@@ -997,11 +980,7 @@ __global__ __launch_bounds__(kOrthBlock) void psgd_orth4_kernel(float* __restric
 // rows: each thread keeps Q[j .. j+3][0 .. r) in registers, P's rows for the band sit in LDS, and
 // the band is streamed with 16-B non-temporal stores (and loads of M for the residual).
 constexpr int kOuterRows = 16;
-#ifdef GRACE_OUTER_ROWS
-constexpr int kOuter4Rows = GRACE_OUTER_ROWS;
-#else
 constexpr int kOuter4Rows = 4;   // A/B (tools/exp_psgd.py): 4-row bands 12.3 us, 2: 12.7, 8-32: 13.4
-#endif
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void psgd_outer_kernel(const float* __restrict__ P, const float* __restrict__ Q,
@@ -1034,11 +1013,7 @@ __global__ __launch_bounds__(256) void psgd_outer_kernel(const float* __restrict
       }
     }
     if (VEC && j + 3 < m) {
-#ifdef GRACE_OUTER_PLAIN
-      if (out) *reinterpret_cast<f32x4v*>(out + i * m + j) = f32x4v{o[0], o[1], o[2], o[3]};
-#else
       if (out) __builtin_nontemporal_store(f32x4v{o[0], o[1], o[2], o[3]}, reinterpret_cast<f32x4v*>(out + i * m + j));
-#endif
       if (res) {
         const f32x4v mv = __builtin_nontemporal_load(reinterpret_cast<const f32x4v*>(M + i * m + j));
         __builtin_nontemporal_store(f32x4v{mv.x - o[0], mv.y - o[1], mv.z - o[2], mv.w - o[3]},
@@ -1125,18 +1100,6 @@ constexpr int kW1Cols = 1024;                 // columns per workgroup
 constexpr int kW1MaxG = 16;                   // m <= 16384
 constexpr int kW1FinBlock = 1024;
 constexpr uint32_t kW1SpinMax = 1u << 22;     // bounded waits (never expected to run out)
-#ifndef GRACE_W1_SPLIT
-#define GRACE_W1_SPLIT 0   // A/B knob (0: all 16 rows' loads in flight at once)
-#endif
-#ifndef GRACE_W1_NT
-#define GRACE_W1_NT 1      // non-temporal loads of M (A/B, one process: compress 34.9 -> 33.7 us)
-#endif
-#ifndef GRACE_W1_XCD
-#define GRACE_W1_XCD 0     // A/B knob: the G column groups of a slab on one XCD
-#endif
-#ifndef GRACE_W1_QNT
-#define GRACE_W1_QNT 1     // non-temporal stores of the Qraw partials (A/B: compress 34.0 -> 32.9 us)
-#endif
 
 #ifdef GRACE_STAMPS   // diagnostic build only: s_memrealtime phase stamps of psgd_w1_pass
 #define W1_STAMP(ws, slot) do { if (threadIdx.x == 0) { if (blockIdx.x == 0 && blockIdx.y == 0) (ws).dbg[slot] = __builtin_amdgcn_s_memrealtime(); \
@@ -1206,19 +1169,7 @@ __global__ __launch_bounds__(kW1Block) void psgd_w1_pass(const float* __restrict
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int cw = w & 3, rw = w >> 2;
   const int G = gridDim.x, SG = gridDim.y;
-  int cg = blockIdx.x, sy = blockIdx.y;
-#if GRACE_W1_XCD
-  {  // XCD-aware placement (A/B): workgroups are dealt to the 8 XCDs round-robin by linear id; the G
-     // column groups of one slab row get ids 8 apart, i.e. one XCD, so the slab's exchange waits on
-     // workgroups that share an L2 and a fabric port rather than on the slowest of G XCDs
-    const int NB = G * SG, L = blockIdx.y * G + blockIdx.x;
-    if (NB % (8 * G) == 0) {
-      const int x = L & 7, j = L >> 3;
-      cg = j % G;
-      sy = x * (NB / 8 / G) + j / G;
-    }
-  }
-#endif
+  const int cg = blockIdx.x, sy = blockIdx.y;
   W1_STAMP(ws, 0);
   W1_SPAN(ws);
   const int64_t jc = (int64_t)cg * kW1Cols + 256 * cw + 4 * lane;
@@ -1252,18 +1203,12 @@ __global__ __launch_bounds__(kW1Block) void psgd_w1_pass(const float* __restrict
     const int64_t lrow = 4 * (int64_t)s + rw;
     f32x4v v[kW1Rows];
 #pragma unroll
-    for (int d = 0; d < kW1Rows; ++d) {        // every load issued before any is used
+    for (int d = 0; d < kW1Rows; ++d) {        // every load issued before any is used, all 16 rows at once
       // wave-uniform row base (scalar) + 32-bit lane offset; a row past n re-reads row n - 1
       const int64_t row = lrow + L * d;
       const float* rowp = M + (row < n ? row : n - 1) * m;
-#if GRACE_W1_SPLIT > 0   // A/B knob: issue the first rows, wait for them, then the rest
-      if (d == GRACE_W1_SPLIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#if GRACE_W1_NT
+      // non-temporal loads of M (A/B, one process: compress 34.9 -> 33.7 us)
       v[d] = __builtin_nontemporal_load(reinterpret_cast<const f32x4v*>(rowp + jo));
-#else
-      v[d] = *reinterpret_cast<const f32x4v*>(rowp + jo);
-#endif
     }
     if (!qstaged) {   // q rows of the group into LDS while M's loads are in flight
       qstaged = true;
@@ -1392,9 +1337,6 @@ __global__ __launch_bounds__(kW1Block) void psgd_w1_pass(const float* __restrict
     for (int s4 = 0; s4 < 4; ++s4)
 #pragma unroll
       for (int c = 0; c < 4; ++c) acc[s4][c] = 0.0;
-#ifdef GRACE_W1_NOQ   // diagnostic A/B build only: no Qraw FMAs (wrong Q)
-    for (int s4 = 0; s4 < 4; ++s4) acc[s4][0] = (double)v[s4][s4];
-#else
 #pragma unroll
     for (int d = 0; d < kW1Rows; ++d) {
       const double* pr = prow[rw * kW1Rows + d];   // wave-uniform: LDS broadcast
@@ -1408,7 +1350,6 @@ __global__ __launch_bounds__(kW1Block) void psgd_w1_pass(const float* __restrict
         acc[s4][3] = fma(mv, p3, acc[s4][3]);
       }
     }
-#endif
     // row waves summed as (rw0 + rw1) + (rw2 + rw3) through two LDS regions laid out element-major
     // (qred[buf][e][256 cw-lanes]: consecutive lanes on consecutive banks), e = 4 s4 + rank
     double* q16a = &qred[0][64 * cw + lane];
@@ -1445,14 +1386,10 @@ __global__ __launch_bounds__(kW1Block) void psgd_w1_pass(const float* __restrict
         const int qp = threadIdx.x + 1024 * h, jl = qp >> 1;
         if ((int64_t)cg * kW1Cols + jl < m) {
           const int cwl = 64 * (jl >> 8) + ((jl & 255) >> 2), e0 = 4 * (jl & 3) + 2 * (qp & 1);
-#if GRACE_W1_QNT   // A/B knob: non-temporal stores of the Qraw partials
+          // non-temporal stores of the Qraw partials (A/B: compress 34.0 -> 32.9 us)
           typedef double f64x2v __attribute__((ext_vector_type(2)));
           __builtin_nontemporal_store(f64x2v{qred[1][e0 * 256 + cwl], qred[1][(e0 + 1) * 256 + cwl]},
                                       reinterpret_cast<f64x2v*>(ws.qpart + gbase + 2 * qp));
-#else
-          *reinterpret_cast<double2*>(ws.qpart + gbase + 2 * qp) =
-              make_double2(qred[1][e0 * 256 + cwl], qred[1][(e0 + 1) * 256 + cwl]);
-#endif
         }
       }
     }
@@ -1739,25 +1676,17 @@ static int p_ksplit(int64_t n, int64_t m, int64_t tc) {
   const int64_t tiles = (n + kTileR - 1) / kTileR;
   if (tiles > kTickets) return 1;
   const int64_t nkt = (m + tc - 1) / tc;
-#ifdef GRACE_P_KS
-  return (int)min((int64_t)GRACE_P_KS, nkt);
-#endif
   int64_t ks = (2048 + tiles - 1) / tiles;                  // aim for >= 2048 workgroups
   if (ks > nkt) ks = nkt;
   if (ks > 64) ks = 64;
   return ks < 1 ? 1 : (int)ks;
 }
 
-#ifndef GRACE_QT_WG
-#define GRACE_QT_WG 1024
-#endif
+constexpr int64_t kQtWg = 1024, kQt4Wg = 256;   // workgroups the Qt kernels' slabs aim for
 static int64_t qt_slab(int64_t n, int64_t m) {
   const int64_t groups = (m + Tile<kCPL>::C - 1) / Tile<kCPL>::C;
   if (groups * 128 > kTickets / 2) return n;
-#ifdef GRACE_QT_SLAB
-  return GRACE_QT_SLAB;
-#endif
-  const int64_t ns = (GRACE_QT_WG + groups - 1) / groups;   // aim for >= GRACE_QT_WG workgroups
+  const int64_t ns = (kQtWg + groups - 1) / groups;   // aim for >= kQtWg workgroups
   int64_t slab = (n + ns - 1) / ns;
   slab = (slab + kTileR - 1) / kTileR * kTileR;
   if (slab < 2 * kTileR) slab = 2 * kTileR;                 // keep the prefetch pipeline busy
@@ -1769,10 +1698,7 @@ static int64_t qt_slab(int64_t n, int64_t m) {
 static bool qt4_ok(int64_t m) { return ((m + kQ4C - 1) / kQ4C) * 16 <= kTickets / 2; }
 static int64_t qt4_slab(int64_t n, int64_t m) {
   const int64_t groups = (m + kQ4C - 1) / kQ4C;
-#ifndef GRACE_QT4_WG
-#define GRACE_QT4_WG 256
-#endif
-  const int64_t ns = (GRACE_QT4_WG + groups - 1) / groups;
+  const int64_t ns = (kQt4Wg + groups - 1) / groups;
   int64_t slab = (n + ns - 1) / ns;
   slab = (slab + 4 * kQ4D - 1) / (4 * kQ4D) * (4 * kQ4D);   // four row waves of whole batches
   while ((n + slab - 1) / slab > 16 * kFan) slab *= 2;
@@ -1828,7 +1754,6 @@ grace_status_t grace_powersgd_qt(const float* M, int64_t n, int64_t m, const flo
   const bool vec = (m % 4 == 0) && ((reinterpret_cast<uintptr_t>(M) & 15u) == 0);
   uint32_t* tickets = reinterpret_cast<uint32_t*>(ws);
   float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + kTicketBytes);
-#ifndef GRACE_QT_MFMA
   if (r == 4 && vec && qt4_ok(m) && ((reinterpret_cast<uintptr_t>(P) & 15u) == 0)) {
     const int64_t slab = qt4_slab(n, m);
     const dim3 grid((unsigned)((m + kQ4C - 1) / kQ4C), (unsigned)((n + slab - 1) / slab));
@@ -1836,7 +1761,6 @@ grace_status_t grace_powersgd_qt(const float* M, int64_t n, int64_t m, const flo
     GRACE_CHECK_LAUNCH("grace_powersgd_qt");
     return GRACE_OK;
   }
-#endif
   const int64_t slab = qt_slab(n, m);
   const int64_t nslab = (n + slab - 1) / slab;
   const dim3 grid((unsigned)((m + Tile<kCPL>::C - 1) / Tile<kCPL>::C), (unsigned)nslab);

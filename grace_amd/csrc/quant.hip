@@ -21,18 +21,9 @@ constexpr int kQBlock = 256;
 // set (tools/exp_tern_ab.py, two boxes): 2 buckets per row beat 4 for every row kernel (fewer
 // registers, more rows in flight); the QSGD encoder is best at <= 4096 workgroups (a few
 // iterations per row: 38 -> 34 us), the decoders at <= 8192 (QSGD 24 -> 22 us, TernGrad 25 -> 21 us).
-#ifndef GRACE_QNB
-#define GRACE_QNB 2
-#endif
-constexpr int kQNB = GRACE_QNB;
-#ifndef GRACE_QGRID
-#define GRACE_QGRID 8192
-#endif
-constexpr int kQGridCap = GRACE_QGRID;      // decoders
-#ifndef GRACE_QENC_GRID
-#define GRACE_QENC_GRID 4096
-#endif
-constexpr int kQEncGridCap = GRACE_QENC_GRID;   // QSGD encoder
+constexpr int kQNB = 2;
+constexpr int kQGridCap = 8192;      // decoders
+constexpr int kQEncGridCap = 4096;   // QSGD encoder
 constexpr int kSegLds = 512;     // offset tables up to this many segments are staged in LDS
 
 // segment containing flat element / bucket index `x`: largest s with off[s] <= x
@@ -226,11 +217,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_kernel(
   // int8 codes leave as 16-B stores: each row stages its kQNB buckets' codes (128 B each) here and
   // every lane stores 16 contiguous bytes (a 4-B store per quad covered four 64-B pieces per wave
   // instruction: 10 of the encoder's 33 us)
-#ifdef GRACE_QSGD_STORE4   // A/B build only: the per-quad 4-B code stores
-  constexpr bool kStage16 = false;
-#else
   constexpr bool kStage16 = !FUSED && sizeof(CodeT) == 1;
-#endif
   const bool codes16 = (reinterpret_cast<uintptr_t>(codes) & 15) == 0;
   __shared__ uint32_t cst[kStage16 ? kQBlock / 16 : 1][kQNB * 32];
   stage_tables32(tab, seg_off, bkt_off, nseg);
@@ -308,11 +295,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_kernel(
 #pragma unroll
           for (int j = 0; j < 4; ++j) uu[j] = eq + j < end[h] ? u[eq + j] : 0.f;
         } else {
-#ifdef GRACE_DIAG_NORNG   // diagnostic A/B build only: constant u
-          uu[0] = uu[1] = uu[2] = uu[3] = 0.5f + 0.f * (float)key;
-#else
           uniform01x4_k(key, (uint32_t)eq + xoff, uu);
-#endif
         }
         CodeT c[4];
 #pragma unroll
@@ -341,9 +324,6 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_kernel(
               (uint32_t)(uint8_t)c[0] | ((uint32_t)(uint8_t)c[1] << 8) | ((uint32_t)(uint8_t)c[2] << 16) |
               ((uint32_t)(uint8_t)c[3] << 24);
         } else {
-#ifdef GRACE_DIAG_NOSTORE   // diagnostic A/B build only: no code stores (a never-true runtime guard)
-          if (norm[h] < 0.f)
-#endif
           store_codes4(codes, eq, end[h], fast[h][q], c);
         }
       }
@@ -356,9 +336,6 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_kernel(
         const int h = h0 + (l16 >> 3);
         if (h < kQNB && ok[h] && st16[h]) {
           const uint4 wv = *reinterpret_cast<const uint4*>(&cst[threadIdx.x >> 4][h * 32 + 4 * (l16 & 7)]);
-#ifdef GRACE_DIAG_NOSTORE
-          if (norm[h] < 0.f)
-#endif
           *reinterpret_cast<uint4*>(codes + (e[h][0] - 4 * l16) + 16 * (l16 & 7)) = wv;
         }
       }
@@ -386,20 +363,8 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_kernel(
 // whole, 16-B aligned 128-element blocks (a segment's partial last bucket, unaligned segments) are
 // skipped by the pipeline and encoded afterwards by their row with per-element loads.
 // ResNet-50 set (25.5 M elements, 199,672 buckets): 36.7 -> 34.2 us.
-#ifndef GRACE_QENC_PIPE
-#define GRACE_QENC_PIPE 1
-#endif
-#ifndef GRACE_QENC_PIPE_GRID
-#define GRACE_QENC_PIPE_GRID 4096   // A/B on the ResNet-50 set: 1024 35.6, 2048 34.6, 4096 34.2 us
-#endif
-constexpr int kQEncPipeGridCap = GRACE_QENC_PIPE_GRID;
-#ifndef GRACE_QENC_PIPE_FUSED
-#define GRACE_QENC_PIPE_FUSED 0
-#endif
+constexpr int kQEncPipeGridCap = 4096;   // A/B on the ResNet-50 set: 1024 35.6, 2048 34.6, 4096 34.2 us
 constexpr int kQBkMax = 1024;   // buckets per workgroup of the pipelined encoder (its LDS table)
-#ifndef GRACE_QENC_NT
-#define GRACE_QENC_NT 1
-#endif
 
 template <typename CodeT, int VARIANT, bool FUSED>
 struct QsgdPipe {
@@ -491,11 +456,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
       for (int q = 0; q < 2; ++q) {
         int32_t e = full ? base + 4 * l16 + 64 * q : 0;
         asm volatile("" : "+v"(e));   // opaque: hipcc would otherwise split the load into a branch
-#if GRACE_QENC_NT
         T.v[h][q] = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(x + e));
-#else
-        T.v[h][q] = *reinterpret_cast<const f4v*>(x + e);
-#endif
       }
     }
   };
@@ -508,11 +469,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const float v4[4] = {T.v[h][q][0], T.v[h][q][1], T.v[h][q][2], T.v[h][q][3]};
-#ifdef GRACE_DIAG_NONORM   // diagnostic A/B build only: no bucket reduction
-        acc[h] += (double)v4[0];
-#else
         acc[h] = P::sq_acc(v4, acc[h]);
-#endif
       }
       acc[h] = row16_sum(acc[h]);
     }
@@ -526,7 +483,8 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
       sc = VARIANT == 0 ? (1.0f / nm) * qf : qf / nm;
       ds = nm / qf;
     };
-    if constexpr (kQNB == 2) {
+    static_assert(kQNB == 2, "even / odd lanes of a row share the two buckets' scalars");
+    {
       float nm, sc, ds;
       scalars(odd ? acc[1] : acc[0], nm, sc, ds);
       auto even = [](float v) {   // quad_perm [0,0,2,2]
@@ -542,17 +500,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
         const bool f = odd ? T.full[1] : T.full[0];
         if (f) norms_out[odd ? T.bb[1] : T.bb[0]] = nm;
       }
-    } else {
-#pragma unroll
-      for (int h = 0; h < kQNB; ++h) {
-        scalars(acc[h], norm[h], scale[h], dsc[h]);
-        if (!FUSED && l16 == 0 && T.full[h]) norms_out[T.bb[h]] = norm[h];
-      }
     }
-#ifdef GRACE_DIAG_NONORM
-#pragma unroll
-    for (int h = 0; h < kQNB; ++h) { norm[h] = (float)acc[h] + 1.f; scale[h] = qf / norm[h]; dsc[h] = norm[h] / qf; }
-#endif
 #pragma unroll
     for (int h = 0; h < kQNB; ++h) {
       if (!T.full[h]) continue;   // row-uniform
@@ -564,11 +512,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
       for (int q = 0; q < 2; ++q) {
         const int32_t eq = base + 4 * l16 + 64 * q;
         float uu[4];
-#ifdef GRACE_DIAG_NORNG   // diagnostic A/B build only: constant u
-        uu[0] = uu[1] = uu[2] = uu[3] = 0.5f + 0.f * (float)bc;
-#else
         P::uniform4(bc + (uint32_t)(64 * q) * kC, klo, khi, uu);
-#endif
         CodeT c[4];
         uint32_t cw = 0;   // the int8 codes packed (kI8)
         float cf[4];       // the codes as floats (FUSED)
@@ -611,9 +555,6 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
           }
           __builtin_nontemporal_store(o, reinterpret_cast<f4v*>(fused_out + eq));
         } else if (kStage16 && st16) {
-#ifdef GRACE_DIAG_NOSTORE   // diagnostic A/B build only: no code stores (a never-true runtime guard)
-          if (norm[h] < 0.f)
-#endif
           cst[row][h * 32 + q * 16 + l16] = cw;
         } else if constexpr (sizeof(CodeT) == 1) {
           *reinterpret_cast<uint32_t*>(codes + eq) = cw;
@@ -631,9 +572,6 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
         const int32_t bs = hi ? T.base[has ? h0 + 1 : h0] : T.base[h0];
         if (fl && codes16 && (bs & 15) == 0) {
           const uint4 wv = *reinterpret_cast<const uint4*>(&cst[row][(h0 + (hi ? 1 : 0)) * 32 + 4 * (l16 & 7)]);
-#ifdef GRACE_DIAG_NOSTORE
-          if (wv.x == 0x12345678u && wv.y == 0x9abcdef0u)
-#endif
           *reinterpret_cast<uint4*>(codes + bs + 16 * (l16 & 7)) = wv;
         }
       }
@@ -1043,18 +981,12 @@ __global__ __launch_bounds__(kQBlock) void qsgd_decode_bkt_kernel(
 // Stage 1 writes f64 partials per work unit (16384 elements); stage 2 (encode) reduces its
 // segment's partials with the whole workgroup in a fixed order (every unit of a segment derives
 // the identical scale), then encodes its unit.  Both stages move 16 B per lane.
-// Where the segment scale is reduced (A/B knob): 0 = the last stats unit of each segment to arrive
-// (agent-scope partials + arrival ticket), 1 = every encode unit of the segment, from the stats
-// kernel's plain partials, at the start of the encode while its first x loads are in flight (the
-// stats kernel then has no arrival tail).  Both sum the partials in unit order: identical scales.
-#ifndef GRACE_TERN_ENC_REDUCE
-#define GRACE_TERN_ENC_REDUCE 1
-#endif
-constexpr bool kTernEncReduce = GRACE_TERN_ENC_REDUCE != 0;
-#ifndef GRACE_TERN_UNIT
-#define GRACE_TERN_UNIT 16384   // A/B, ResNet-50 set compress: 4096 / 8192 / 16384 / 32768 -> 64.7 /
-#endif                          // 56.5 / 54.0 / 60.6 us (tools/ab_quant.py, one process)
-constexpr int kTernUnit = GRACE_TERN_UNIT;
+// The segment scale is reduced by every encode unit of the segment, from the stats kernel's plain
+// partials, at the start of the encode while its first x loads are in flight: the stats kernel has
+// no arrival tail.  (The alternative, the last stats unit of each segment to arrive reducing
+// agent-scope partials behind an arrival ticket, gave identical scales and lost.)
+constexpr int kTernUnit = 16384;   // A/B, ResNet-50 set compress: 4096 / 8192 / 16384 / 32768 -> 64.7 /
+                                   // 56.5 / 54.0 / 60.6 us (tools/ab_quant.py, one process)
 
 struct TernPartial { double sum, sq; float amax; uint32_t nan; };
 
@@ -1105,27 +1037,21 @@ __device__ __forceinline__ TernPartial block_tern_reduce(double sum, double sq, 
   return p;
 }
 
-// per-segment scale slot, kept at the segment's first unit (empty segments have none)
 struct TernScale { float c, scalar; };
 
-// Per-unit workspace slot, an array of structs indexed by unit: a unit's counter sits at the same
-// address whatever nunits a call uses and no call's partials overlap another call's counters, so one
-// zero-initialised buffer serves calls of any shape (each segment's last unit leaves its counter
-// zeroed).  A struct-of-arrays layout sized by nunits let a smaller call's partials land on a larger
-// call's counters.
+// Per-unit workspace slot, an array of structs indexed by unit, so one buffer serves calls of any
+// shape.  Only the partial is used; the rest keeps the 40-byte slot (grace_terngrad_slot_bytes) that
+// callers size their workspaces by.
 struct TernSlot {
-  TernPartial part;    // the unit's partial (agent-scope stores)
-  TernScale scale;     // the segment's (c, scalar), at its first unit
-  uint32_t tick, pad;  // arrivals, at the segment's first unit
+  TernPartial part;    // the unit's partial
+  TernScale scale;     // (unused)
+  uint32_t tick, pad;  // (unused)
 };
 static_assert(sizeof(TernSlot) == 40, "TernSlot layout");
 __host__ __device__ inline size_t tern_ws_bytes(int64_t nunits) { return sizeof(TernSlot) * (size_t)(nunits + 1); }
 
-// Stage 1: per-unit f64 partials; the LAST unit of a segment to arrive reduces the segment's
-// partials in a fixed order (the same block reduction whichever unit it is, so the scale is
-// deterministic) and publishes (c, scalar) for stage 2.  Partials cross workgroups -- and XCDs,
-// whose L2s are not coherent -- so they are written and read back at agent scope (write-through),
-// ordered by vmcnt(0) before the arrival ticket: no cache-wide fences.
+// Stage 1: per-unit f64 partials, plain stores: the encode kernel (the next launch) reduces each
+// segment's partials itself.
 // unit0 / xoff (sharded TernGrad, grace_terngrad_shard_*): this launch runs the global units unit0,
 // unit0 + 1, ... and x points at global element xoff (its shard); 0 / 0 for a whole bucket
 __global__ __launch_bounds__(kQBlock) void tern_stats_kernel(const float* __restrict__ x,
@@ -1135,7 +1061,6 @@ __global__ __launch_bounds__(kQBlock) void tern_stats_kernel(const float* __rest
                                                             float* __restrict__ scalars, int64_t unit0 = 0,
                                                             int64_t xoff = 0) {
   __shared__ SegTables tab;
-  __shared__ uint32_t s_last;
   const SegView sv = stage_tables(tab, seg_off, unit_off, nseg);
   const int64_t unit = unit0 + blockIdx.x;
   const int s = find_seg(sv.sub, nseg, unit);
@@ -1160,62 +1085,10 @@ __global__ __launch_bounds__(kQBlock) void tern_stats_kernel(const float* __rest
     tern_acc(v.w, sum, sq, amax, nan);
   }
   const TernPartial p = block_tern_reduce(sum, sq, amax, nan);
-  uint64_t* pw = reinterpret_cast<uint64_t*>(&w[unit].part);
-  if constexpr (kTernEncReduce) {
-    // the encode kernel reduces the segment's partials itself (next launch: plain stores suffice)
-    if (t == 0) w[unit].part = p;
-    return;
-  }
-  if (t == 0) {
-    __hip_atomic_store(pw, (uint64_t)__double_as_longlong(p.sum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(pw + 1, (uint64_t)__double_as_longlong(p.sq), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(pw + 2, (uint64_t)__float_as_uint(p.amax) | ((uint64_t)p.nan << 32), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int64_t first = sv.sub[s], units = sv.sub[s + 1] - first;
-    s_last = atomicAdd(&w[first].tick, 1u) == (uint32_t)(units - 1);
-  }
-  __syncthreads();
-  if (!s_last) return;
-  // last arrival: the segment's statistics from its units' partials, in a fixed order
-  const int64_t first = sv.sub[s];
-  sum = 0.0; sq = 0.0; amax = 0.f; nan = 0;
-  for (int64_t j = first + t; j < sv.sub[s + 1]; j += kQBlock) {
-    const uint64_t* pj = reinterpret_cast<const uint64_t*>(&w[j].part);
-    sum += __longlong_as_double((long long)__hip_atomic_load(pj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    sq += __longlong_as_double((long long)__hip_atomic_load(pj + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    const uint64_t mn = __hip_atomic_load(pj + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    amax = fmaxf(amax, __uint_as_float((uint32_t)mn));
-    nan |= (uint32_t)(mn >> 32);
-  }
-  const TernPartial q = block_tern_reduce(sum, sq, amax, nan);
-  if (t == 0) {
-    float c;
-    if (clip_in) {
-      c = clip_in[s];
-    } else {
-      const double nn = (double)(sv.seg[s + 1] - sv.seg[s]);
-      const double mean = q.sum / nn;
-      double var = q.sq / nn - mean * mean;
-      if (var < 0.0) var = 0.0;
-      c = (float)(2.5 * (double)(float)sqrt(var));
-    }
-    // torch.clamp propagates a NaN bound (an injected NaN clip, or std = NaN when x holds an inf):
-    // every clamped element and the scalar are then NaN, as for a NaN element
-    const float scalar = (q.nan || c != c) ? __int_as_float(0x7FC00000) : fminf(q.amax, c);
-    w[first].scale = TernScale{c, scalar};
-    scalars[s] = scalar;
-    w[first].tick = 0u;   // left zeroed for the next call
-  }
+  if (t == 0) w[unit].part = p;
 }
 
-#ifndef GRACE_TERN_BLOCK
-#define GRACE_TERN_BLOCK 256
-#endif
-constexpr int kTernBlock = GRACE_TERN_BLOCK;
-#ifndef GRACE_TERN_SUB
-#define GRACE_TERN_SUB 4
-#endif   // encode workgroup (A/B: 256 beats 512 and 1024)
+constexpr int kTernBlock = 256;   // encode workgroup (A/B: 256 beats 512 and 1024)
 
 // FUSED: the world-1 Allgather step in the same pass -- out = 0 + code * scalar (the decoder's
 // arithmetic, division by 1 omitted) written instead of the codes: bit-identical to encode + decode.
@@ -1247,7 +1120,7 @@ __global__ __launch_bounds__(kTernBlock) void tern_encode_kernel(
   // the ResNet-50 set are co-resident, so loading the whole unit first made the chip load, then
   // compute, then store in lockstep, with HBM idle in between.)
   constexpr int kPer = kTernUnit / 4 / kTernBlock;
-  constexpr int kTernSub = GRACE_TERN_SUB;
+  constexpr int kTernSub = 4;
   constexpr int kTernSteps = kPer / kTernSub;
   static_assert(kPer % kTernSub == 0, "sub-chunks tile the unit");
   const f4v* xq = reinterpret_cast<const f4v*>(x + qs.a0);
@@ -1258,17 +1131,13 @@ __global__ __launch_bounds__(kTernBlock) void tern_encode_kernel(
       // plain (cache-allocating) loads: part of the re-read of x hits the Infinity Cache the
       // statistics pass filled (A/B r04, one box: encode 29.6 us with non-temporal loads, 27.8 us
       // plain; 32.5 us when a 512 MiB write stream between the two passes evicts x first)
-#ifdef GRACE_TERN_ENC_NT   // A/B build only: the non-temporal re-read
-      if (nq > 0) dst[k] = __builtin_nontemporal_load(xq + (j < nq ? j : 0));
-#else
       if (nq > 0) dst[k] = xq[j < nq ? j : 0];
-#endif
     }
   };
   f4v cur[kTernSub], nxt[kTernSub];
   load_sub(0, cur);
   float c, scalar;
-  if constexpr (kTernEncReduce) {
+  {
     // the segment's statistics from its units' partials, in unit order (every unit of the segment
     // computes the identical scale); the first unit publishes the scalar
     double ps = 0.0, pq = 0.0;
@@ -1290,10 +1159,6 @@ __global__ __launch_bounds__(kTernBlock) void tern_encode_kernel(
     }
     scalar = (q.nan || c != c) ? __int_as_float(0x7FC00000) : fminf(q.amax, c);   // (NaN bound: NaN)
     if (t == 0 && unit == sv.sub[s] && scalars) scalars[s] = scalar;
-  } else {
-    const TernScale sc = w[sv.sub[s]].scale;   // published by the segment's last stats unit
-    c = sc.c;
-    scalar = sc.scalar;
   }
 
   auto enc = [&](float xv, float ui) -> int8_t {
@@ -1606,59 +1471,9 @@ __global__ __launch_bounds__(kQBlock) void tern_decode_kernel(const int8_t* __re
   }
 }
 
-// A/B knob (r06): a tile decoder -- one 16-B output quad per lane and QPT quads per lane, i.e. a
-// contiguous 4 KB x QPT output tile per workgroup (r05's write probes: a workgroup writing 4 KB runs
-// at the box's write rate, 16 KB tiles at 0.87 of it) -- instead of the 16-lane row decoder.  World 1.
-// Measured slower (tools/ab_decode.py, ResNet-50 set, one process): row decoder 22.4 us, tiles of
-// 4 / 8 / 16 KB 26.6 / 24.1 / 24.2 us (the per-workgroup segment-table staging and search); off.
-#ifndef GRACE_TERN_TILE_QPT
-#define GRACE_TERN_TILE_QPT 0
-#endif
-constexpr int kTernTileQpt = GRACE_TERN_TILE_QPT;
-
-template <int QPT>
-__global__ __launch_bounds__(kQBlock) void tern_decode_tile_kernel(const int8_t* __restrict__ codes,
-                                                                  const float* __restrict__ scalars,
-                                                                  const int64_t* __restrict__ seg_off, int nseg,
-                                                                  int64_t n, float divisor, int aggregate,
-                                                                  float* __restrict__ out) {
-  __shared__ int64_t sg[kSegLds + 1];
-  for (int i = threadIdx.x; i <= nseg; i += blockDim.x) sg[i] = seg_off[i];
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * kQBlock * 4 * QPT + 4 * threadIdx.x;
-  uint32_t cw[QPT];
-  int sq[QPT];
-  bool fast[QPT];
-#pragma unroll
-  for (int q = 0; q < QPT; ++q) {   // every load issued first, unconditionally (clamped address)
-    const int64_t e = base + (int64_t)q * kQBlock * 4;
-    sq[q] = find_seg(sg, nseg, e < n ? e : n - 1);
-    fast[q] = e + 3 < n && e + 3 < sg[sq[q] + 1];
-    cw[q] = *reinterpret_cast<const uint32_t*>(codes + (fast[q] ? e : 0));
-  }
-#pragma unroll
-  for (int q = 0; q < QPT; ++q) {
-    const int64_t e = base + (int64_t)q * kQBlock * 4;
-    if (e >= n) continue;
-    if (fast[q]) {
-      const float sc = scalars[sq[q]];
-      float a[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float d = (float)(int8_t)((cw[q] >> (8 * j)) & 0xFFu) * sc;
-        a[j] = aggregate ? 0.f + d : d;
-        if (divisor != 1.0f) a[j] = a[j] / divisor;
-      }
-      __builtin_nontemporal_store(f4v{a[0], a[1], a[2], a[3]}, reinterpret_cast<f4v*>(out + e));
-    } else {
-      for (int64_t x = e; x < e + 4 && x < n; ++x) {
-        const float d = (float)codes[x] * scalars[find_seg(sg, nseg, x)];
-        float v = aggregate ? 0.f + d : d;
-        out[x] = divisor == 1.0f ? v : v / divisor;
-      }
-    }
-  }
-}
+// (r06: a tile decoder, a contiguous 4 / 8 / 16 KB output tile per workgroup instead of the 16-lane
+// row decoder, was slower on the ResNet-50 set: 26.6 / 24.1 / 24.2 us against 22.4 us -- the
+// per-workgroup segment-table staging and search; tools/ab_decode.py)
 
 // Sharded TernGrad (grace_amd/dist/sharded_terngrad.py): the whole bucket decoded straight from the
 // gathered per-rank records.  Rank w's codes of its elements [rank_lo[w], rank_lo[w + 1]) sit in
@@ -2110,13 +1925,6 @@ static unsigned qenc_pipe_grid(int64_t nbuckets) {
   return (unsigned)std::max<int64_t>(stream_grid(nbuckets, kQNB * kQBlock / 16, kQEncPipeGridCap), need);
 }
 
-#ifdef GRACE_TERN_FLUSH
-__global__ void tern_flush_kernel(float* p, int64_t n) {
-  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * blockDim.x * 4)
-    *reinterpret_cast<float4*>(p + i) = make_float4(1.f, 2.f, 3.f, 4.f);
-}
-#endif
-
 extern "C" {
 
 grace_status_t grace_qsgd_step_w1(const float* x, const int64_t* seg_off, const int64_t* bkt_off, int32_t nseg,
@@ -2130,16 +1938,11 @@ grace_status_t grace_qsgd_step_w1(const float* x, const int64_t* seg_off, const 
   hipStream_t st = as_stream(stream);
   // the fused step keeps the non-pipelined kernel: it writes 4 B per element, and the A/B on the
   // ResNet-50 set had the pipelined one slower there (43.1 / 40.6 us at 1024 / 2048 workgroups vs 40.3)
-  const bool pipe = GRACE_QENC_PIPE_FUSED && !u;
-  const unsigned grid16 = pipe ? qenc_pipe_grid(nbuckets) : stream_grid(nbuckets, kQNB * kQBlock / 16, kQEncGridCap);
+  const unsigned grid16 = stream_grid(nbuckets, kQNB * kQBlock / 16, kQEncGridCap);
 #define GRACE_QSTEP128(CT, V)                                                                        \
-  do { if (pipe)                                                                                          \
-    qsgd_encode128_pipe_kernel<CT, V, true><<<grid16, kQBlock, 0, st>>>(                             \
-        x, seg_off, bkt_off, nseg, (int32_t)nbuckets, (float)quantum_num, seed, nullptr, nullptr, out); \
-  else                                                                                               \
-    qsgd_encode128_kernel<CT, V, true><<<grid16, kQBlock, 0, st>>>(x, seg_off, bkt_off, nseg, (int32_t)nbuckets, \
+  qsgd_encode128_kernel<CT, V, true><<<grid16, kQBlock, 0, st>>>(x, seg_off, bkt_off, nseg, (int32_t)nbuckets, \
                                                                 (float)quantum_num, u, seed, nullptr, nullptr, \
-                                                                nullptr, out); } while (0)
+                                                                nullptr, out)
   if (variant == 1) GRACE_QSTEP128(int8_t, 1);
   else if (quantum_num < 128) GRACE_QSTEP128(int8_t, 0);
   else GRACE_QSTEP128(__half, 0);
@@ -2162,7 +1965,7 @@ grace_status_t grace_qsgd_compress_at(const float* x, int64_t xoff, const int64_
   const unsigned grid = stream_grid(nbuckets, kQNB * kQBlock / 32, kQGridCap);
   hipStream_t st = as_stream(stream);
   if (bucket_size == 128 && nseg <= kSegLds && nbuckets < (int64_t(1) << 24)) {   // n < 2^31
-    const bool pipe = GRACE_QENC_PIPE && !u && !norms_in && xoff == 0;
+    const bool pipe = !u && !norms_in && xoff == 0;
     const unsigned grid16 = pipe ? qenc_pipe_grid(nbuckets) : stream_grid(nbuckets, kQNB * kQBlock / 16, kQEncGridCap);
 #define GRACE_QENC128(CT, V)                                                                         \
   do { if (pipe)                                                                                          \
@@ -2339,16 +2142,6 @@ grace_status_t grace_terngrad_compress(const float* x, const int64_t* seg_off, c
   tern_stats_kernel<<<(unsigned)nunits, kQBlock, 0, as_stream(stream)>>>(x, seg_off, unit_off, nseg, clip_in, w,
                                                                        scalars);
   GRACE_CHECK_LAUNCH("grace_terngrad_compress");
-#ifdef GRACE_TERN_FLUSH
-  // diagnostic A/B build only: stream 512 MiB of writes between the statistics pass and the
-  // encoder, so the encoder's re-read of x cannot be served by the 256 MiB Infinity Cache
-  {
-    static float* junk = nullptr;
-    constexpr int64_t kJunk = (int64_t)1 << 27;
-    if (!junk && hipMalloc(&junk, kJunk * sizeof(float)) != hipSuccess) junk = nullptr;
-    if (junk) tern_flush_kernel<<<4096, 256, 0, as_stream(stream)>>>(junk, kJunk);
-  }
-#endif
   if (u)
     tern_encode_kernel<false, true><<<(unsigned)nunits, kTernBlock, 0, as_stream(stream)>>>(
         x, seg_off, unit_off, nseg, w, u, seed, codes, nullptr, clip_in, scalars);
@@ -2364,8 +2157,6 @@ int32_t grace_terngrad_slot_bytes(void) { return (int32_t)sizeof(TernSlot); }
 grace_status_t grace_terngrad_shard_stats(const float* x, int64_t xoff, const int64_t* seg_off,
                                           const int64_t* unit_off, int32_t nseg, int64_t unit0, int64_t nunits_local,
                                           void* ws, void* stream) {
-  GRACE_REQUIRE(kTernEncReduce, "grace_terngrad_shard_stats: needs the encode-side scale reduction "
-                "(a GRACE_TERN_ENC_REDUCE=0 build has no global slot protocol)");
   GRACE_REQUIRE(x && seg_off && unit_off && nseg >= 1 && unit0 >= 0 && nunits_local >= 0 && xoff >= 0 && ws &&
                     (reinterpret_cast<uintptr_t>(x) & 15) == 0,
                 "grace_terngrad_shard_stats: bad arguments (16-B aligned shard)");
@@ -2380,8 +2171,6 @@ grace_status_t grace_terngrad_shard_encode(const float* x, int64_t xoff, const i
                                            const int64_t* unit_off, int32_t nseg, int64_t unit0,
                                            int64_t nunits_local, const float* clip_in, const float* u, uint64_t seed,
                                            int8_t* codes, const void* ws, void* stream) {
-  GRACE_REQUIRE(kTernEncReduce, "grace_terngrad_shard_encode: needs the encode-side scale reduction "
-                "(a GRACE_TERN_ENC_REDUCE=0 build has no global slot protocol)");
   GRACE_REQUIRE(x && seg_off && unit_off && nseg >= 1 && unit0 >= 0 && nunits_local >= 0 && xoff >= 0 && codes &&
                     ws && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(u) |
                             reinterpret_cast<uintptr_t>(codes)) & 15) == 0,
@@ -2435,16 +2224,6 @@ grace_status_t grace_terngrad_decompress(const int8_t* codes, const float* scala
                 "grace_terngrad_decompress: bad arguments");
   if (n == 0) return GRACE_OK;
   const int vec = (code_stride % 4 == 0) && ((uintptr_t)codes % 4 == 0);
-  if constexpr (kTernTileQpt > 0) {
-    if (world == 1 && vec && nseg <= kSegLds && (uintptr_t)out % 16 == 0) {
-      constexpr int64_t kTile = (int64_t)kQBlock * 4 * (kTernTileQpt > 0 ? kTernTileQpt : 1);
-      tern_decode_tile_kernel<(kTernTileQpt > 0 ? kTernTileQpt : 1)><<<(unsigned)((n + kTile - 1) / kTile), kQBlock, 0,
-                                                                     as_stream(stream)>>>(
-          codes, scalars, seg_off, nseg, n, divisor, aggregate, out);
-      GRACE_CHECK_LAUNCH("grace_terngrad_decompress");
-      return GRACE_OK;
-    }
-  }
   if (nseg <= kSegLds && n < (int64_t(1) << 31)) {
     tern_decode_row_kernel<<<stream_grid((n + 127) / 128, kQNB * kQBlock / 16, kQGridCap), kQBlock, 0,
                              as_stream(stream)>>>(codes, scalars, code_stride, scal_stride, world, seg_off, nseg,

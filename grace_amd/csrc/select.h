@@ -123,11 +123,7 @@ template <int BLOCK = 1024, typename Src>
 __device__ uint64_t block_select_comp(const Src& src, int64_t N, uint32_t need, uint32_t* hist,
                                       uint32_t* s_w, uint32_t* s_res, int first_pass = 0,
                                       uint64_t prefix0 = 0, uint64_t pmask0 = 0) {
-#ifdef GRACE_SELECT_U1   // A/B build only
-  constexpr int kU = 1;
-#else
   constexpr int kU = 4;   // items per thread per round, all loaded before any is counted
-#endif
   uint64_t prefix = prefix0, pmask = pmask0;
   uint32_t rem = need;
   for (int p = first_pass; p < 6; ++p) {
@@ -152,11 +148,7 @@ __device__ uint64_t block_select_comp(const Src& src, int64_t N, uint32_t need, 
     rem -= above;
     prefix |= (uint64_t)d << shift;
     pmask |= (uint64_t)dmask << shift;
-#ifdef GRACE_SELECT_NOEARLY   // A/B build only
-    const bool whole = false;
-#else
     const bool whole = hist[d] == rem;   // LDS, identical for every thread
-#endif
     __syncthreads();
     if (whole) break;
   }

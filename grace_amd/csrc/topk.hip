@@ -53,23 +53,13 @@ template <int MODE> constexpr bool kWritesOut = MODE == kDenseFused || MODE == k
 // the main pass writes provisional picks as selected; the finalize fixes up its candidates
 template <int MODE> constexpr bool kProv = kWritesOut<MODE> || MODE == kResSwap;
 
-#ifndef GRACE_MAIN_BLOCK
-#define GRACE_MAIN_BLOCK 256
-#endif
-#ifndef GRACE_MAIN_VEC
-#define GRACE_MAIN_VEC 12
-#endif
-constexpr int kMainBlock = GRACE_MAIN_BLOCK;
-constexpr int kMainVec = GRACE_MAIN_VEC;                   // float4 per thread
+constexpr int kMainBlock = 256;
+constexpr int kMainVec = 12;                               // float4 per thread
 constexpr int kMainChunk = kMainBlock * 4 * kMainVec;      // 12288 elements per workgroup (A/B, 256 MiB
                                                            // top-k 1 % + residual: 8192 / 12288 / 16384 /
                                                            // 20480 / 24576 -> 240 / 195 / 196.5 / 204 / 205 us)
-#ifndef GRACE_MAIN_VEC_12B
-#define GRACE_MAIN_VEC_12B 20
-#endif
-#ifndef GRACE_MAIN_VEC_NORES
-#define GRACE_MAIN_VEC_NORES 32
-#endif
+constexpr int kMainVec12B = 20;                            // float4 per thread at 12 B per element
+constexpr int kMainVecNoRes = 32;                          // ... and at 4 / 8 B per element
 // Chunk length by the bytes the pass moves per element: each workgroup has fixed costs (histogram
 // clear and flush, list flushes), so the fewer bytes per element, the longer its chunk.  A/B at
 // 256 MiB (main pass):
@@ -82,23 +72,17 @@ template <bool HAS_RES, int MODE>
 constexpr int kBytesOf = 4 + (HAS_RES ? 4 : 0) + (kWritesR<MODE> ? 4 : 0) + (kWritesOut<MODE> ? 4 : 0);
 template <bool HAS_RES, int MODE>
 constexpr int kVecOf = kBytesOf<HAS_RES, MODE> >= 16 ? kMainVec
-                       : (kBytesOf<HAS_RES, MODE> >= 12 ? GRACE_MAIN_VEC_12B : GRACE_MAIN_VEC_NORES);
+                       : (kBytesOf<HAS_RES, MODE> >= 12 ? kMainVec12B : kMainVecNoRes);
 template <bool HAS_RES, int MODE> constexpr int kChunkOf = kMainBlock * 4 * kVecOf<HAS_RES, MODE>;
 // (r05 A/B at BASELINE configs[4]'s 8.4 M-element shard, 12 B per element: 410 chunks of 20480
 // leave CUs with 1-2 workgroups, yet chunks of 16384 (512, two per CU) or 12288 (683) ran the local
 // step in 57.5-58.4 / 59.2-60.3 us against 57.3-57.4 -- the small bucket's main pass is bound by
 // its per-workgroup latency, not by the balance; 8192 spills 176-200 B with the residual stream)
 constexpr int kHistBins = 2048;                            // candidate histogram
-constexpr int kStage = 1024;                               // LDS staging entries per list (all waves)
+constexpr int kStage = 1024;                               // half the LDS staging entries (all waves)
 constexpr int kSelBlock = 1024;                            // single-workgroup selectors
 constexpr int kSmallN = 32768;                             // single-workgroup path
-constexpr int kSampleRunLen = 16;
-constexpr int kSampleRuns = 2048;
-constexpr int kSample = kSampleRuns * kSampleRunLen;       // 32768 keys, 32 per thread
-#ifndef GRACE_FIN_BLOCKS
-#define GRACE_FIN_BLOCKS 128
-#endif
-constexpr int kFinBlocks = GRACE_FIN_BLOCKS;
+constexpr int kFinBlocks = 128;
 constexpr int kFinPer = 8;                                 // candidates per thread per round
 
 
@@ -136,10 +120,7 @@ static_assert(sizeof(TopkCtl) == 64, "ctl layout");
 #endif
 #define STAMP(ctlp, slot) STAMP_IF(blockIdx.x == 0, ctlp, slot)
 
-#ifndef GRACE_SAMPLE_MAX
-#define GRACE_SAMPLE_MAX 131072
-#endif
-constexpr int kSampleMax = GRACE_SAMPLE_MAX;               // stratified sample size
+constexpr int kSampleMax = 131072;                         // stratified sample size
 // The sample a bucket's bracket draws: every element up to kSampleMax, else kSampleMax.  (r05
 // A/B at BASELINE configs[4]'s 8.4 M-element shard: one sample per 256 elements, 32 K instead of
 // 131 K, took the bracket from 16.6 to 14.1 us but doubled the candidates, finalize 11.8 -> 17.0
@@ -152,36 +133,11 @@ __host__ __device__ inline int64_t bracket_sample_n(int64_t n) {
   const int64_t cap = n <= kHalfSampleMaxN ? kSampleMax / 2 : kSampleMax;
   return n < cap ? n : cap;
 }
-constexpr int kSampleBlock = 1024;
-#ifndef GRACE_BRACKET_BLOCK
-#define GRACE_BRACKET_BLOCK 1024
-#endif
 // single-GPU bracket: one sample per thread.  A/B (step, one process): 1024 -> 232 us, 512 -> 236-240
 // (twice the workgroups, each still one per CU for the 136 KB of LDS histograms), 256 -> 256
-constexpr int kBracketBlock = GRACE_BRACKET_BLOCK;
+constexpr int kBracketBlock = 1024;
 constexpr int kBracketBins = 32768;                        // key >> 16: 1/64-octave bins
-#ifndef GRACE_SAMPLE_RUN
-#define GRACE_SAMPLE_RUN 1
-#endif
-constexpr int kBracketRun = GRACE_SAMPLE_RUN;              // adjacent elements per sampling thread
 constexpr int kCoarseBins = 2048;                          // key >> 20: 1/8-octave bins
-// A/B knob: the bracket's search in every main-pass workgroup instead of the bracket's last sampler.
-// Measured slower (r05, tools/ab_main_search.sh, profiles/r05_main_search_ab.txt): headline step
-// 0.2330-0.2373 vs 0.2294-0.2314 ms, topk_main 204-209 vs 198-200 us -- 5462 workgroups x 2096
-// agent-scope histogram loads (46 MB at the memory side) and a search latency at every
-// workgroup's start cost more than the bracket's tail they remove.
-#ifndef GRACE_MAIN_SEARCH
-#define GRACE_MAIN_SEARCH 0
-#endif
-constexpr bool kMainSearch = GRACE_MAIN_SEARCH != 0;       // the bracket's search in the main pass
-constexpr int kHistStride = 1;
-// copies of the bracket's sample histograms (workgroup b flushes into copy b % kSampleCopies; the
-// search sums them): same-address device atomics serialise, and every sampling workgroup adds to
-// the same popular bins
-#ifndef GRACE_SAMPLE_COPIES
-#define GRACE_SAMPLE_COPIES 1
-#endif
-constexpr int kSampleCopies = GRACE_SAMPLE_COPIES;
 
 // Workspace layout.  Every counter / histogram region is left zeroed by the step that used it
 // (the select kernel re-zeroes what the next step accumulates into), so the caller only has to
@@ -226,11 +182,11 @@ static TopkWs carve(void* ws, int64_t n, int64_t k) {
   w.fb = reinterpret_cast<uint32_t*>(p);
   p += align256(sizeof(uint32_t) * kFbWordsHost);
   w.hist = reinterpret_cast<uint32_t*>(p);
-  p += align256(sizeof(uint32_t) * kHistBins * kHistStride);
+  p += align256(sizeof(uint32_t) * kHistBins);
   w.chist = reinterpret_cast<uint32_t*>(p);
-  p += align256(sizeof(uint32_t) * kCoarseBins * kSampleCopies);
+  p += align256(sizeof(uint32_t) * kCoarseBins);
   w.shist = reinterpret_cast<uint32_t*>(p);
-  p += align256(sizeof(uint32_t) * kBracketBins * kSampleCopies);
+  p += align256(sizeof(uint32_t) * kBracketBins);
   w.cand = reinterpret_cast<int2*>(p);
   p += align256(sizeof(int2) * w.cap);
   w.bnd = reinterpret_cast<int2*>(p);
@@ -241,9 +197,9 @@ static TopkWs carve(void* ws, int64_t n, int64_t k) {
 
 static size_t ws_bytes(int64_t n, int64_t k) {
   const int64_t cap = topk_cap(n, k);
-  return 256 + align256(sizeof(uint32_t) * kHistBins * kHistStride) +
-         align256(sizeof(uint32_t) * kCoarseBins * kSampleCopies) +
-         align256(sizeof(uint32_t) * kBracketBins * kSampleCopies) +
+  return 256 + align256(sizeof(uint32_t) * kHistBins) +
+         align256(sizeof(uint32_t) * kCoarseBins) +
+         align256(sizeof(uint32_t) * kBracketBins) +
          2 * align256(sizeof(int2) * cap) + align256(sizeof(uint32_t) * kFbWordsHost);
 }
 
@@ -365,7 +321,8 @@ __device__ __forceinline__ float compensate(const StepArgs& a, int64_t i) {
 // sample: every thread takes one element from its stratum of n / sample_n at a hashed offset
 // (single elements, so spatially correlated gradients do not inflate the sample variance) and
 // counts its key's top 16 bits (key >> 16: 1/64-octave bins) in an LDS histogram; non-zero bins
-// are flushed with one global atomic each.
+// are flushed with one global atomic each.  (One sample per thread is fastest: the strided samples
+// are latency-bound random loads that want many waves.)
 // select: reads the 32768-bin histogram with coalesced loads, finds both bracketing sample ranks
 // with one block scan, rounds the thresholds OUTWARD to bin edges (the rounding only widens the
 // candidate band) and re-zeroes the histogram and every counter the next kernels accumulate into.
@@ -380,22 +337,10 @@ __device__ __forceinline__ int64_t sample_pos(int64_t sidx, uint32_t st) {
   return sidx * (int64_t)st + off;
 }
 
-#ifndef GRACE_SAMPLE_PER
-#define GRACE_SAMPLE_PER 1
-#endif
-#ifndef GRACE_SAMPLE_DEFF
-#define GRACE_SAMPLE_DEFF 1.0
-#endif
 // variance inflation allowed for in the bracket's margin (design effect of clustered samples)
-constexpr double kSampleDeff = GRACE_SAMPLE_DEFF;
-#ifndef GRACE_SAMPLE_SIGMA
-#define GRACE_SAMPLE_SIGMA 6.0
-#endif
-constexpr double kSampleSigma = GRACE_SAMPLE_SIGMA;        // bracket half-width in binomial sigmas
+constexpr double kSampleDeff = 1.0;
+constexpr double kSampleSigma = 6.0;                       // bracket half-width in binomial sigmas
 constexpr double kSurePoisson = 1e-6;                      // small-sample "sure" rank: miss probability
-constexpr int kSamplePer = GRACE_SAMPLE_PER;               // samples per thread: 1 is fastest --
-                                                           // the strided samples are latency-bound
-                                                           // random loads that want many waves
 
 // The sample ranks (descending, 0-based) that bracket the k-th largest of n with ~kSampleSigma
 // binomial sigmas, and the sample's own estimate of the k-th rank (the provisional threshold);
@@ -484,13 +429,7 @@ __device__ __forceinline__ BracketThr bracket_search(const StepArgs& a, const To
   uint32_t hc[kCPT], hs = 0;
 #pragma unroll
   for (int c = 0; c < kCPT; ++c) {
-    uint32_t x[kSampleCopies];
-#pragma unroll
-    for (int q = 0; q < kSampleCopies; ++q)
-      x[q] = __hip_atomic_load(w.chist + q * kCoarseBins + top - c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    hc[c] = 0;
-#pragma unroll
-    for (int q = 0; q < kSampleCopies; ++q) hc[c] += x[q];
+    hc[c] = __hip_atomic_load(w.chist + top - c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     hs += hc[c];
   }
   if (tid < 6) s_fc[tid] = 0;
@@ -515,14 +454,7 @@ __device__ __forceinline__ BracketThr bracket_search(const StepArgs& a, const To
     const bool act = q < 3;
     const uint32_t bin = act ? s_fc[2 * q] * 16 + (15 - j) : 0u;
     uint32_t v = 0u;
-    if (act) {
-      uint32_t x[kSampleCopies];
-#pragma unroll
-      for (int c = 0; c < kSampleCopies; ++c)
-        x[c] = __hip_atomic_load(w.shist + c * kBracketBins + bin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-      for (int c = 0; c < kSampleCopies; ++c) v += x[c];
-    }
+    if (act) v = __hip_atomic_load(w.shist + bin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
     for (int o = 1; o < 16; o <<= 1) {
       const uint32_t u = __shfl_up(v, o, 16);
@@ -572,7 +504,7 @@ constexpr int kClearMax = 96;                   // clear workgroups at most
 template <bool HAS_RES>
 __global__ __launch_bounds__(kBracketBlock) void topk_bracket(StepArgs a, TopkWs w) {
   // workgroups past the sample grid clear the recycled output (no ticket: not part of the sample)
-  const unsigned nsamp = (unsigned)((a.sample_n / kBracketRun + kBracketBlock - 1) / kBracketBlock);
+  const unsigned nsamp = (unsigned)((a.sample_n + kBracketBlock - 1) / kBracketBlock);
   if (blockIdx.x >= nsamp) {
     clear_prev(a, blockIdx.x - nsamp, gridDim.x - nsamp);
     return;
@@ -587,68 +519,50 @@ __global__ __launch_bounds__(kBracketBlock) void topk_bracket(StepArgs a, TopkWs
   STAMP(w.ctl, 0);
   const uint32_t st = (uint32_t)a.stratum;
   const int64_t sidx = (int64_t)blockIdx.x * kBracketBlock + tid;
-  // kBracketRun > 1 (A/B builds): every thread takes a run of adjacent elements at a hashed,
-  // run-aligned offset in a stratum of kBracketRun * stratum elements -- fewer DRAM rows opened
-  // per sample, at the price of samples that are no longer independent on correlated buckets
-  const bool valid = sidx * kBracketRun < a.sample_n;
-  float t[kBracketRun];
-#pragma unroll
-  for (int q = 0; q < kBracketRun; ++q) t[q] = 0.f;
+  const bool valid = sidx < a.sample_n;
+  // (a one-element array filled and read by loops, not a scalar: the scalar form compiles to the
+  // same instructions with the kernel's argument loads scheduled differently)
+  float t[1];
+  for (int q = 0; q < 1; ++q) t[q] = 0.f;
   if (valid) {
-    if constexpr (kBracketRun == 1) {
-#ifdef GRACE_SAMPLE_SEQ   // diagnostic A/B build only: contiguous sample positions
-      t[0] = compensate<HAS_RES>(a, sidx);
-#else
-      const int64_t pos = sample_pos(sidx, st);
-      if (HAS_RES && a.rs_in) {
-        // carried t'(pos) of this residual's previous step and that step's selection threshold:
-        // r'(pos) exactly as its main pass + finalize left it, from one random DRAM read (g) per
-        // sample instead of two
-        const float tp = a.rs_in[sidx];
-        const uint64_t Tp = *reinterpret_cast<const uint64_t*>(a.rs_in + carry_thr_off(a.sample_n));
-        const float gv = a.g[pos];
-        const float rp = comp_key(abs_key(tp), (uint32_t)pos) >= Tp ? tp - tp : tp;
-        t[0] = a.beta * rp + a.gamma * gv;
-      } else {
-        t[0] = compensate<HAS_RES>(a, pos);
-      }
-      if (a.rs_out) a.rs_out[sidx] = t[0];   // this step's t(pos), for the next step's bracket
-#endif
+    const int64_t pos = sample_pos(sidx, st);
+    if (HAS_RES && a.rs_in) {
+      // carried t'(pos) of this residual's previous step and that step's selection threshold:
+      // r'(pos) exactly as its main pass + finalize left it, from one random DRAM read (g) per
+      // sample instead of two
+      const float tp = a.rs_in[sidx];
+      const uint64_t Tp = *reinterpret_cast<const uint64_t*>(a.rs_in + carry_thr_off(a.sample_n));
+      const float gv = a.g[pos];
+      const float rp = comp_key(abs_key(tp), (uint32_t)pos) >= Tp ? tp - tp : tp;
+      t[0] = a.beta * rp + a.gamma * gv;
     } else {
-      const uint32_t off = (uint32_t)(((uint64_t)hash32((uint32_t)sidx * 0x9E3779B9u + 0x5EEDu) * st) >> 32) *
-                           kBracketRun;
-      const int64_t i0 = sidx * (int64_t)st * kBracketRun + off;
-#pragma unroll
-      for (int q = 0; q < kBracketRun; ++q) t[q] = compensate<HAS_RES>(a, i0 + q);
+      t[0] = compensate<HAS_RES>(a, pos);
     }
+    if (a.rs_out) a.rs_out[sidx] = t[0];   // this step's t(pos), for the next step's bracket
   }
   // counters of this step's main / finalize passes (their previous users have completed)
   if (blockIdx.x == 0 && tid >= 3 && tid < 12) reinterpret_cast<uint32_t*>(w.ctl)[tid] = 0u;
   if (blockIdx.x < (unsigned)(kHistBins / kBracketBlock))
-    w.hist[(blockIdx.x * kBracketBlock + tid) * kHistStride] = 0u;
+    w.hist[blockIdx.x * kBracketBlock + tid] = 0u;
   for (int b = tid; b < kBracketBins; b += kBracketBlock) lh[b] = 0;
   for (int b = tid; b < kCoarseBins; b += kBracketBlock) lc[b] = 0;
   __syncthreads();
   STAMP(w.ctl, 1);
   if (valid) {
-#pragma unroll
-    for (int q = 0; q < kBracketRun; ++q) {
+    for (int q = 0; q < 1; ++q) {
       const uint32_t key = abs_key(t[q]);
       atomicAdd(&lh[key >> 16], 1u);
       atomicAdd(&lc[key >> 20], 1u);
     }
   }
   __syncthreads();
-  const int cp = (int)(blockIdx.x % kSampleCopies);
   for (int b = tid; b < kBracketBins; b += kBracketBlock)
-    if (lh[b]) atomicAdd(&w.shist[cp * kBracketBins + b], lh[b]);
+    if (lh[b]) atomicAdd(&w.shist[b], lh[b]);
   for (int b = tid; b < kCoarseBins; b += kBracketBlock)
-    if (lc[b]) atomicAdd(&w.chist[cp * kCoarseBins + b], lc[b]);
+    if (lc[b]) atomicAdd(&w.chist[b], lc[b]);
   STAMP(w.ctl, 2);
-  // kMainSearch: no last arriver here -- every main-pass workgroup runs the search itself, a kernel
-  // boundary later (the tail of waiting for the last sampler and one workgroup's search leaves the
-  // chain, as the payload grouping's histogram pass did)
-  if constexpr (kMainSearch) return;
+  // (r05: this search in every main-pass workgroup instead of the last sampler here was 4 us slower
+  // per step -- 5462 workgroups x 2096 agent-scope histogram loads; profiles/r05_main_search_ab.txt)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (tid == 0) s_last = atomicAdd(&w.ctl->bticket, 1u) == nsamp - 1;
@@ -674,15 +588,7 @@ __global__ __launch_bounds__(kBracketBlock) void topk_bracket(StepArgs a, TopkWs
 // per lane).  Per group every lane flags its elements with key >= lo, a DPP wave scan of the
 // counts places them in the wave's own LDS region (no atomic), and the staged entries leave with
 // one global atomic per list and workgroup at the end, sorted into sure / candidate there.
-#ifndef GRACE_MAIN_GROUP
-#define GRACE_MAIN_GROUP 4
-#endif
-constexpr int kGroup = GRACE_MAIN_GROUP;
-#ifndef GRACE_MAIN_RING
-#define GRACE_MAIN_RING 0
-#endif
-constexpr bool kMainRing = GRACE_MAIN_RING != 0;   // main_chunk_v2's copy-free load ring (A/B knob)
-
+constexpr int kGroup = 4;
 
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
   const int lane = threadIdx.x & 63;
@@ -727,18 +633,17 @@ __device__ __forceinline__ void load_group(const StepArgs& a, int64_t gbase, flo
 }
 
 constexpr int kMainWaves = kMainBlock / 64;
-constexpr int kStageWave = kStage / kMainWaves;            // each wave's own region of each list
 
 struct MainShared {
   uint32_t hist[kHistBins];
-  // v3: ONE staged list of flagged elements, kListWave entries per wave (sure / candidate decided at
-  // the flush); v2 (A/B build): sure = list[0 .. kStage), candidates = list[kStage .. 2 kStage)
+  // ONE staged list of flagged elements, kListWave entries per wave (sure / candidate decided at
+  // the flush)
   int2 list[2 * kStage];
-  uint32_t wcnt[kMainWaves];   // each wave's staged count (v2: packed sure | cand << 16), for the flush
+  uint32_t wcnt[kMainWaves];   // each wave's staged count, for the flush
   uint32_t gbase[2];           // the chunk's reservations in the global sure / candidate lists
-  uint32_t cnt[2];             // v3 flush: the chunk's sure / candidate counts, then their positions
+  uint32_t cnt[2];             // flush: the chunk's sure / candidate counts, then their positions
 };
-constexpr int kListWave = 2 * kStage / kMainWaves;         // v3: each wave's region of the one list
+constexpr int kListWave = 2 * kStage / kMainWaves;         // each wave's region of the one list
 
 // wave-wide inclusive scan of one uint32 per lane: DPP row shifts within each 16-lane row, then
 // the row broadcasts (gfx9 row_bcast:15 / row_bcast:31) -- 6 VALU, no LDS, no loop
@@ -752,141 +657,22 @@ __device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
   return v;
 }
 
-// v2 classification of one group (kGroup float4 per lane per array, already loaded): a DPP wave
-// scan of the lanes' packed 16|16 counts places the entries in the wave's OWN regions of the two
-// LDS lists at its running fill (wfill, wave-uniform) -- no reservation atomic (r05: the per-lane
-// ds_add_rtn of r04 became the compiler's atomic-optimizer loop, a readlane / writelane per active
-// lane); one branch per flagged element position for both lists; the candidate histogram is built
-// from the staged entries at the flush instead of a masked ds_add per element.  Returns the wave's
-// new fill.
+// Classification of one group (kGroup float4 per lane per array, already loaded).  The r05 SQ
+// counters of the no-memory main pass (4 B read per element, profiles/r06_nomem_sq_summary.json)
+// showed 2640 VALU instructions per wave for 128 elements per lane -- 20 per element, 35 us of the
+// SIMDs' issue time against a 43 us read stream, half of them in the r05 engine's walk over the 16
+// element positions of a group (one divergent block per position that any lane flagged, ~10 of 16
+// with ~15 flagged elements per wave and group).  This one (r06) keeps per element only what every
+// element needs: its dense outputs, if any, and ONE flag bit (key >= lo) shifted into a per-lane
+// 16-bit mask -- a compare and an add-with-carry.  The flagged elements (~1.5 %) are then visited by
+// a per-lane set-bit loop whose trip count is the wave's largest popcount (typically 2), which
+// classifies them exactly and stages them in the wave's region of ONE LDS list at its running fill
+// (wfill, wave-uniform; a DPP wave scan of the lanes' counts, no reservation atomic); the flush
+// splits sure entries from candidates.  Returns the wave's new fill.
 // UNIT: beta = gamma = 1, t = r + g (1 * x is x bit for bit, so this is the reference's
 // beta * r + gamma * g).
-template <bool HAS_RES, int MODE, bool FAST, bool SKEL = false, bool SPARSE = false, bool UNIT = false>
-__device__ __forceinline__ uint32_t classify_group(const StepArgs& a, const TopkWs& w, MainShared& sm, uint32_t lo,
-                                                   uint32_t hi, uint32_t sh, uint32_t mid, int64_t gbase,
-                                                   const float4 (&rc)[kGroup], const float4 (&gc)[kGroup],
-                                                   uint32_t wfill) {
-  const int64_t n = a.n;
-  float4 t[kGroup];
-  uint32_t msure = 0, mcand = 0;   // bit u*4+j
-#pragma unroll
-  for (int u = 0; u < kGroup; ++u) {
-    if constexpr (HAS_RES && UNIT) {
-      t[u].x = rc[u].x + gc[u].x;
-      t[u].y = rc[u].y + gc[u].y;
-      t[u].z = rc[u].z + gc[u].z;
-      t[u].w = rc[u].w + gc[u].w;
-    } else if constexpr (HAS_RES) {
-      t[u].x = a.beta * rc[u].x + a.gamma * gc[u].x;
-      t[u].y = a.beta * rc[u].y + a.gamma * gc[u].y;
-      t[u].z = a.beta * rc[u].z + a.gamma * gc[u].z;
-      t[u].w = a.beta * rc[u].w + a.gamma * gc[u].w;
-    } else {
-      t[u] = gc[u];
-    }
-    const int64_t i0 = gbase + (int64_t)u * (kMainBlock * 4);
-    float4 rout = t[u], dout = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float tv = comp4(t[u], j);
-      const uint32_t key = abs_key(tv);
-#ifdef GRACE_MAIN_STREAM_ONLY   // diagnostic A/B build only: the streaming ceiling of this layout
-      constexpr bool kSkel = true;
-#else
-      constexpr bool kSkel = SKEL;
-#endif
-      // SKEL (grace_topk_stream_probe): the same loads and stores with no classification -- the
-      // streaming ceiling of this exact layout (nothing is listed; the per-chunk flushes still run)
-      //
-      // The flags are integer arithmetic on the 31-bit keys (sign bits of differences that cannot
-      // overflow), not comparisons: 16 comparisons per group became 16 live 64-bit lane masks, and
-      // the compiler spilled SGPRs to VGPR lanes (r05: 31 spills, 349 v_readlane in topk_main).
-      const uint32_t vbit = (FAST || i0 + j < n) ? 1u : 0u;
-      const uint32_t f_sure = kSkel ? 0u : ((hi - key) >> 31) & vbit;              // key > hi
-      const uint32_t f_lo = kSkel ? 0u : (((key - lo) >> 31) ^ 1u) & vbit;         // key >= lo
-      msure |= f_sure << (u * 4 + j);
-      mcand |= (f_lo & (f_sure ^ 1u)) << (u * 4 + j);
-      if constexpr (kProv<MODE>) {
-        // sure elements, and candidates above the provisional threshold, are written as selected;
-        // the finalize fixes up only the candidates whose final decision differs.  lo <= mid <= hi
-        // (bracket_publish), so "sure or (candidate and key > mid)" is key > mid: an all-ones
-        // mask selects r' = t - t and out = 0 + t bitwise
-        const uint32_t m = kSkel ? 0u : (uint32_t)((int32_t)(mid - key) >> 31) & (0u - vbit);
-        set4(rout, j, u2f((f2u(tv - tv) & m) | (f2u(tv) & ~m)));
-        if constexpr (kWritesOut<MODE>) {
-          set4(dout, j, u2f(f2u(0.f + tv) & m));
-          // recycled output: only the selected elements are written (the rest is already zero)
-          if constexpr (SPARSE) if (m) a.out[i0 + j] = 0.f + tv;
-        }
-      }
-    }
-    if constexpr (kWritesR<MODE>) st4<FAST>(a.r, i0, n, rout);
-    if constexpr (kWritesOut<MODE> && !SPARSE) st4<FAST>(a.out, i0, n, dout);
-  }
-  if constexpr (SKEL) return wfill;
-  const uint32_t msel = msure | mcand;
-  const uint32_t cnt = __popc(msure) | (__popc(mcand) << 16);
-  const uint32_t incl = wave_incl_scan_dpp(cnt);
-  const uint32_t tot = __builtin_amdgcn_readlane(incl, 63);
-  if (msel) {
-    const uint32_t cs = cnt & 0xFFFFu, cc = cnt >> 16;
-    const uint32_t bse = wfill + incl - cnt;   // this lane's first slots in the wave's regions
-    uint32_t ps = bse & 0xFFFFu, pc = bse >> 16;
-    const uint32_t wb = (threadIdx.x >> 6) * kStageWave;
-    // entries past the wave's region spill to the global lists (rare: one global atomic per lane)
-    const uint32_t over_s = ps + cs > (uint32_t)kStageWave ? min(ps + cs - (uint32_t)kStageWave, cs) : 0u;
-    const uint32_t over_c = pc + cc > (uint32_t)kStageWave ? min(pc + cc - (uint32_t)kStageWave, cc) : 0u;
-    uint32_t gs = 0, gcn = 0;
-    if (over_s) gs = atomicAdd(&w.ctl->n_sure, over_s);
-    if (over_c) gcn = atomicAdd(&w.ctl->n_cand, over_c);
-#pragma unroll
-    for (int u = 0; u < kGroup; ++u) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int b = u * 4 + j;
-        if ((msel >> b) & 1u) {
-          const int64_t i = gbase + (int64_t)u * (kMainBlock * 4) + j;
-          const float tv = comp4(t[u], j);
-          const int2 e = make_int2((int)i, (int)f2u(tv));
-          if ((msure >> b) & 1u) {
-            if (ps < (uint32_t)kStageWave) {
-              sm.list[wb + ps] = e;
-            } else if (gs < (uint32_t)a.k) {
-              a.vals[gs] = tv; a.idx[gs] = (int32_t)(e.x + a.idx_base); ++gs;
-            }
-            ++ps;
-          } else {
-            if (pc < (uint32_t)kStageWave) {
-              sm.list[kStage + wb + pc] = e;
-            } else {
-              atomicAdd(&sm.hist[cand_bin(abs_key(tv), lo, sh)], 1u);
-              if (gcn < (uint32_t)w.cap) w.cand[gcn] = e;
-              ++gcn;
-            }
-            ++pc;
-          }
-        }
-      }
-    }
-  }
-  return wfill + tot;
-}
-
-// ------------------------------------------------------------------------------------------------
-// v3 classification (r06).  The r05 SQ counters of the no-memory main pass (4 B read per element,
-// profiles/r06_nomem_sq_summary.json) showed 2640 VALU instructions per wave for 128 elements per
-// lane -- 20 per element, 35 us of the SIMDs' issue time against a 43 us read stream, half of them
-// in v2's walk over the 16 element positions of a group (one divergent block per position that any
-// lane flagged, ~10 of 16 with ~15 flagged elements per wave and group).  v3 keeps per element only
-// what every element needs: its dense outputs, if any, and ONE flag bit (key >= lo) shifted into a
-// per-lane 16-bit mask -- a compare and an add-with-carry.  The flagged elements (~1.5 %) are then
-// visited by a per-lane set-bit loop whose trip count is the wave's largest popcount (typically 2),
-// which classifies them exactly and stages them in the wave's region of ONE LDS list; the flush
-// splits sure entries from candidates.
-#ifndef GRACE_MAIN_V2
-#define GRACE_MAIN_V2 0
-#endif
-constexpr bool kMainV3 = GRACE_MAIN_V2 == 0;   // A/B knob: 1 builds the r05 classification
+// SKEL (grace_topk_stream_probe): the same loads and stores with no classification -- the streaming
+// ceiling of this exact layout (nothing is listed).
 
 // t[e >> 2].(e & 3) of a lane whose element e is known only at run time: a select tree on e's bits
 __device__ __forceinline__ float sel16(const float4 (&t)[4], uint32_t e) {
@@ -916,16 +702,11 @@ __device__ __forceinline__ void spill_entry(const StepArgs& a, const TopkWs& w, 
 }
 
 template <bool HAS_RES, int MODE, bool FAST, bool SKEL = false, bool SPARSE = false, bool UNIT = false>
-__device__ __forceinline__ uint32_t classify_group_v3(const StepArgs& a, const TopkWs& w, MainShared& sm, uint32_t lo,
-                                                      uint32_t hi, uint32_t sh, uint32_t mid, int64_t gbase,
-                                                      const float4 (&rc)[kGroup], const float4 (&gc)[kGroup],
-                                                      uint32_t wfill) {
+__device__ __forceinline__ uint32_t classify_group(const StepArgs& a, const TopkWs& w, MainShared& sm, uint32_t lo,
+                                                   uint32_t hi, uint32_t sh, uint32_t mid, int64_t gbase,
+                                                   const float4 (&rc)[kGroup], const float4 (&gc)[kGroup],
+                                                   uint32_t wfill) {
   static_assert(kGroup == 4, "sel16 picks from 4 float4 per lane");
-#ifdef GRACE_MAIN_STREAM_ONLY   // diagnostic A/B build only: the streaming ceiling of this layout
-  constexpr bool kSkel = true;
-#else
-  constexpr bool kSkel = SKEL;
-#endif
   // the exact provisional decision (key > mid) per element, where a dense output depends on it
   constexpr bool kDenseProv = kProv<MODE> && (kWritesR<MODE> || (kWritesOut<MODE> && !SPARSE));
   const int64_t n = a.n;
@@ -958,7 +739,7 @@ __device__ __forceinline__ uint32_t classify_group_v3(const StepArgs& a, const T
         // (r' = t - t, out = 0 + t); the finalize fixes up the candidates it decides otherwise.
         // lo <= mid <= hi (bracket_publish), so that set is key > mid
         const uint32_t key = abs_key(tv);
-        const bool sel = !kSkel && key > mid;
+        const bool sel = !SKEL && key > mid;
         set4(rout, j, sel ? tv - tv : tv);
         if constexpr (kWritesOut<MODE> && !SPARSE) set4(dout, j, sel ? 0.f + tv : 0.f);
         f = key >= lo;
@@ -968,7 +749,7 @@ __device__ __forceinline__ uint32_t classify_group_v3(const StepArgs& a, const T
         f = !(fabsf(tv) < lo_f);
       }
       if (!FAST) f = f && i0 + j < n;
-      if (kSkel) f = false;
+      if (SKEL) f = false;
       m = m + m + (f ? 1u : 0u);
     }
     if constexpr (kWritesR<MODE>) st4<FAST>(a.r, i0, n, rout);
@@ -1014,12 +795,13 @@ __device__ __forceinline__ uint32_t classify_group_v3(const StepArgs& a, const T
   return wfill + tot;
 }
 
-// v3 flush: the waves' regions are concatenated; one pass counts sure / candidate entries with wave
-// ballots, one reservation per list and chunk, a second pass writes them (wave ballot ranks, one LDS
-// add per wave and list); candidates are counted into the LDS histogram there
-template <bool SPARSE_OUT>
-__device__ __forceinline__ void flush_staged_v3(const StepArgs& a, const TopkWs& w, MainShared& sm, uint32_t lo,
-                                                uint32_t hi, uint32_t sh, uint32_t mid, uint32_t wfill) {
+// The staged list of one chunk leaves: the waves' regions are concatenated; one pass counts sure /
+// candidate entries with wave ballots, one reservation per list and chunk, a second pass writes them
+// (wave ballot ranks, one LDS add per wave and list); candidates are counted into the LDS histogram
+// there
+template <bool SPARSE_OUT = false>
+__device__ __forceinline__ void flush_staged(const StepArgs& a, const TopkWs& w, MainShared& sm, uint32_t lo,
+                                             uint32_t hi, uint32_t sh, uint32_t mid, uint32_t wfill) {
   const int tid = threadIdx.x;
   if ((tid & 63) == 0) sm.wcnt[tid >> 6] = min(wfill, (uint32_t)kListWave);
   if (tid == 0) sm.cnt[0] = 0u;
@@ -1047,14 +829,10 @@ __device__ __forceinline__ void flush_staged_v3(const StepArgs& a, const TopkWs&
   __syncthreads();
   if (tid == 0) {
     const uint32_t c = sm.cnt[0], ns = c & 0xFFFFu, nc = c >> 16;
-#ifdef GRACE_DIAG_NORESERVE   // timing-only A/B build (wrong results): no atomic return to wait for
-    sm.gbase[0] = (uint32_t)((blockIdx.x * 97u) % (uint32_t)(a.k > 2048 ? a.k - 2048 : 1));
-    sm.gbase[1] = (uint32_t)((blockIdx.x * 53u) % (uint32_t)(w.cap > 2048 ? w.cap - 2048 : 1));
-    (void)ns; (void)nc;
-#else
+    // one reservation per chunk and list (5461 per step on each counter: as 8 copies, a timing-only
+    // build, the main pass was 2 us faster in 196 -- within the spread, so the one counter stays)
     sm.gbase[0] = ns ? atomicAdd(&w.ctl->n_sure, ns) : 0u;
     sm.gbase[1] = nc ? atomicAdd(&w.ctl->n_cand, nc) : 0u;
-#endif
     sm.cnt[0] = 0u;
     sm.cnt[1] = 0u;
   }
@@ -1089,31 +867,31 @@ __device__ __forceinline__ void flush_staged_v3(const StepArgs& a, const TopkWs&
   __syncthreads();   // the list and wcnt are free for the next chunk
 }
 
+// classify_group for the rotating-copy loops of main_chunk.  Only an extra level of inlining, but
+// without it hipcc orders two index adds of those loops differently; kept so that the kernels stay
+// instruction for instruction what was measured.
 template <bool HAS_RES, int MODE, bool FAST, bool SKEL = false, bool SPARSE = false, bool UNIT = false>
 __device__ __forceinline__ uint32_t classify_group_sel(const StepArgs& a, const TopkWs& w, MainShared& sm, uint32_t lo,
                                                        uint32_t hi, uint32_t sh, uint32_t mid, int64_t gbase,
                                                        const float4 (&rc)[kGroup], const float4 (&gc)[kGroup],
                                                        uint32_t wfill) {
-  if constexpr (kMainV3)
-    return classify_group_v3<HAS_RES, MODE, FAST, SKEL, SPARSE, UNIT>(a, w, sm, lo, hi, sh, mid, gbase, rc, gc, wfill);
-  else
-    return classify_group<HAS_RES, MODE, FAST, SKEL, SPARSE, UNIT>(a, w, sm, lo, hi, sh, mid, gbase, rc, gc, wfill);
+  return classify_group<HAS_RES, MODE, FAST, SKEL, SPARSE, UNIT>(a, w, sm, lo, hi, sh, mid, gbase, rc, gc, wfill);
 }
 
 template <bool HAS_RES, int MODE, bool FAST, bool SKEL = false, bool SPARSE = false, bool UNIT = false,
           int NV = kVecOf<HAS_RES, MODE>>
-__device__ __forceinline__ uint32_t main_chunk_v2(const StepArgs& a, const TopkWs& w, MainShared& sm,
-                                                  uint32_t lo, uint32_t hi, uint32_t sh, uint32_t mid, int64_t chunk) {
+__device__ __forceinline__ uint32_t main_chunk(const StepArgs& a, const TopkWs& w, MainShared& sm,
+                                               uint32_t lo, uint32_t hi, uint32_t sh, uint32_t mid, int64_t chunk) {
   constexpr int NG = NV / kGroup;
   static_assert(NG * kGroup == NV, "groups tile the chunk (group 2 / 3 / 6 lost 0-5 %, A/B)");
   const int64_t cbase = chunk * (kMainBlock * 4 * NV) + (int64_t)threadIdx.x * 4;
   uint32_t wfill = 0;
-  if constexpr (kMainV3 && FAST) {
-    // v3: the group loop fully unrolled over a static ring of R group buffers (R - 1 groups' loads
-    // in flight ahead of the one being classified).  Every load is unconditional at compile time:
-    // a load that a run-time condition may skip (the r05 ring's `q + R - 1 < NG`), or a rotating
-    // copy of the next group's buffer into the current one (v2), made hipcc wait vmcnt(0) -- for
-    // every load in flight -- once per group
+  if constexpr (FAST) {
+    // the group loop fully unrolled over a static ring of R group buffers (R - 1 groups' loads in
+    // flight ahead of the one being classified).  Every load is unconditional at compile time: a
+    // load that a run-time condition may skip (a rolled ring's `q + R - 1 < NG`, r05), or a rotating
+    // copy of the next group's buffer into the current one (the loops below), made hipcc wait
+    // vmcnt(0) -- for every load in flight -- once per group
     constexpr int R = HAS_RES ? 2 : 3;   // buffers: 2 x (r, g) or 3 x g
     constexpr int64_t S = (int64_t)kGroup * (kMainBlock * 4);
     float4 rb[R][kGroup], gb[R][kGroup];
@@ -1126,39 +904,13 @@ __device__ __forceinline__ uint32_t main_chunk_v2(const StepArgs& a, const TopkW
       // loads and spill (the unrolled ring at 128 VGPRs with 15-70 spilled)
       __builtin_amdgcn_sched_barrier(0);
       if (q + R - 1 < NG) load_group<HAS_RES, FAST>(a, cbase + (q + R - 1) * S, rb[(q + R - 1) % R], gb[(q + R - 1) % R]);
-      wfill = classify_group_v3<HAS_RES, MODE, FAST, SKEL, SPARSE, UNIT>(a, w, sm, lo, hi, sh, mid, cbase + q * S,
-                                                                         rb[q % R], gb[q % R], wfill);
+      wfill = classify_group<HAS_RES, MODE, FAST, SKEL, SPARSE, UNIT>(a, w, sm, lo, hi, sh, mid, cbase + q * S,
+                                                                      rb[q % R], gb[q % R], wfill);
     }
     return wfill;
   }
-  if constexpr (kMainRing) {
-    // A static ring of R group buffers, R - 1 groups' loads in flight ahead of the one being
-    // classified: the loop body is unrolled over the R slots, so no buffer is ever copied.  (The
-    // rotating copies of the loops below, next -> current after each group, made hipcc wait
-    // vmcnt(0) -- for the next group's loads AND the stores just issued -- before every group: each
-    // wave's memory pipeline drained once per group.)
-    constexpr int R = HAS_RES ? 2 : 3;   // buffers: 2 x (r, g) or 3 x g, 64 / 48 VGPRs
-    constexpr int64_t S = (int64_t)kGroup * (kMainBlock * 4);
-    float4 rb[R][kGroup], gb[R][kGroup];
-#pragma unroll
-    for (int p = 0; p < R - 1; ++p)
-      if (p < NG) load_group<HAS_RES, FAST>(a, cbase + p * S, rb[p], gb[p]);
-#pragma unroll 1
-    for (int q0 = 0; q0 < NG; q0 += R) {
-#pragma unroll
-      for (int j = 0; j < R; ++j) {
-        const int q = q0 + j;
-        if (q < NG) {   // workgroup-uniform
-          if (q + R - 1 < NG) load_group<HAS_RES, FAST>(a, cbase + (q + R - 1) * S, rb[(j + R - 1) % R], gb[(j + R - 1) % R]);
-          wfill = classify_group_sel<HAS_RES, MODE, FAST, SKEL, SPARSE, UNIT>(a, w, sm, lo, hi, sh, mid, cbase + q * S,
-                                                                          rb[j], gb[j], wfill);
-        }
-      }
-    }
-    return wfill;
-  }
+  // FAST = false (the bucket's tail, unaligned buffers): rotating copies, next -> current
   float4 rc[kGroup], gc[kGroup];
-#ifndef GRACE_MAIN_PREFETCH1   // A/B build only: one group ahead on every stream
   if constexpr (!HAS_RES && NG >= 3) {
     // one input stream (g only): the loads run TWO groups ahead, so a lane keeps as many bytes in
     // flight as with the residual stream (8 x 16 B)
@@ -1175,7 +927,6 @@ __device__ __forceinline__ uint32_t main_chunk_v2(const StepArgs& a, const TopkW
     }
     return wfill;
   }
-#endif
   load_group<HAS_RES, FAST>(a, cbase, rc, gc);
 #pragma unroll 1
   for (int q = 0; q < NG; ++q) {
@@ -1189,64 +940,6 @@ __device__ __forceinline__ uint32_t main_chunk_v2(const StepArgs& a, const TopkW
   return wfill;
 }
 
-// the staged lists of one chunk leave with one global atomic per list: the waves' regions are
-// concatenated in wave order (v2: the staged candidates are counted into the LDS histogram here)
-__device__ __forceinline__ void flush_staged_v2(const StepArgs& a, const TopkWs& w, MainShared& sm, uint32_t lo,
-                                                uint32_t sh, uint32_t wfill) {
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) sm.wcnt[tid >> 6] = wfill;
-  __syncthreads();
-  uint32_t os[kMainWaves + 1], oc[kMainWaves + 1];
-  os[0] = oc[0] = 0;
-#pragma unroll
-  for (int v = 0; v < kMainWaves; ++v) {
-    const uint32_t f = sm.wcnt[v];
-    os[v + 1] = os[v] + min(f & 0xFFFFu, (uint32_t)kStageWave);
-    oc[v + 1] = oc[v] + min(f >> 16, (uint32_t)kStageWave);
-  }
-  const uint32_t ns = os[kMainWaves], nc = oc[kMainWaves];
-  if (tid == 0) {
-    // one reservation per chunk and list (5461 per step on each counter: as 8 copies, a timing-only
-    // build, the main pass was 2 us faster in 196 -- within the spread, so the one counter stays)
-#ifdef GRACE_DIAG_NORESERVE   // timing-only A/B build (wrong results): no atomic return to wait for
-    sm.gbase[0] = (uint32_t)((blockIdx.x * 97u) % (uint32_t)(a.k > 2048 ? a.k - 2048 : 1));
-    sm.gbase[1] = (uint32_t)((blockIdx.x * 53u) % (uint32_t)(w.cap > 2048 ? w.cap - 2048 : 1));
-#else
-    sm.gbase[0] = ns ? atomicAdd(&w.ctl->n_sure, ns) : 0u;
-    sm.gbase[1] = nc ? atomicAdd(&w.ctl->n_cand, nc) : 0u;
-#endif
-  }
-  __syncthreads();
-  for (uint32_t j = tid; j < ns; j += kMainBlock) {
-    const uint32_t gp = sm.gbase[0] + j;
-    if (gp < (uint32_t)a.k) {
-      int v = 0;
-#pragma unroll
-      for (int x = 1; x < kMainWaves; ++x) v += j >= os[x];
-      const int2 e = sm.list[v * kStageWave + (j - os[v])];
-      a.vals[gp] = u2f((uint32_t)e.y);
-      a.idx[gp] = (int32_t)(e.x + a.idx_base);
-    }
-  }
-  for (uint32_t j = tid; j < nc; j += kMainBlock) {
-    const uint32_t gp = sm.gbase[1] + j;
-    int v = 0;
-#pragma unroll
-    for (int x = 1; x < kMainWaves; ++x) v += j >= oc[x];
-    const int2 e = sm.list[kStage + v * kStageWave + (j - oc[v])];
-    atomicAdd(&sm.hist[cand_bin(abs_key(u2f((uint32_t)e.y)), lo, sh)], 1u);
-    if (gp < (uint32_t)w.cap) w.cand[gp] = e;
-  }
-  __syncthreads();   // the lists and wcnt are free for the next chunk
-}
-
-template <bool SPARSE_OUT = false>
-__device__ __forceinline__ void flush_staged(const StepArgs& a, const TopkWs& w, MainShared& sm, uint32_t lo,
-                                             uint32_t hi, uint32_t sh, uint32_t mid, uint32_t wfill) {
-  if constexpr (kMainV3) flush_staged_v3<SPARSE_OUT>(a, w, sm, lo, hi, sh, mid, wfill);
-  else flush_staged_v2(a, w, sm, lo, sh, wfill);
-}
-
 // NV: float4 per lane per chunk
 template <bool HAS_RES, int MODE, bool VEC, bool SKEL = false, bool SPARSE = false, int NV = kVecOf<HAS_RES, MODE>>
 __global__ __launch_bounds__(kMainBlock, 4) void topk_main(StepArgs a, TopkWs w) {   // <= 128 VGPRs: 4 WGs/CU
@@ -1258,15 +951,7 @@ __global__ __launch_bounds__(kMainBlock, 4) void topk_main(StepArgs a, TopkWs w)
   if constexpr (!SKEL) {
     for (int b = tid; b < kHistBins; b += kMainBlock) sm.hist[b] = 0;
   }
-  uint32_t lo, hi, sh, mid;
-  if constexpr (kMainSearch && !SKEL) {
-    __shared__ uint32_t s_w[kMainBlock / kWave + 1], s_fc[6], s_res[3];
-    const BracketThr t = bracket_search<kMainBlock>(a, w, s_w, s_fc, s_res);
-    lo = t.lo; hi = t.hi; sh = t.sh; mid = t.mid;
-    if (blockIdx.x == 0 && tid == 0) bracket_publish(w.ctl, t);   // for the finalize (next launch)
-  } else {
-    lo = w.ctl->thr_lo; hi = w.ctl->thr_hi; sh = w.ctl->shift; mid = w.ctl->thr_mid;
-  }
+  const uint32_t lo = w.ctl->thr_lo, hi = w.ctl->thr_hi, sh = w.ctl->shift, mid = w.ctl->thr_mid;
   constexpr int64_t kCh = (int64_t)kMainBlock * 4 * NV;
   const int64_t nchunks = (a.n + kCh - 1) / kCh;
   const bool unit = HAS_RES && a.beta == 1.f && a.gamma == 1.f;
@@ -1276,11 +961,11 @@ __global__ __launch_bounds__(kMainBlock, 4) void topk_main(StepArgs a, TopkWs w)
   for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
     uint32_t wfill;
     if (VEC && (chunk + 1) * kCh <= a.n && unit)
-      wfill = main_chunk_v2<HAS_RES, MODE, VEC, SKEL, SPARSE, true, NV>(a, w, sm, lo, hi, sh, mid, chunk);
+      wfill = main_chunk<HAS_RES, MODE, VEC, SKEL, SPARSE, true, NV>(a, w, sm, lo, hi, sh, mid, chunk);
     else if (VEC && (chunk + 1) * kCh <= a.n)
-      wfill = main_chunk_v2<HAS_RES, MODE, VEC, SKEL, SPARSE, false, NV>(a, w, sm, lo, hi, sh, mid, chunk);
+      wfill = main_chunk<HAS_RES, MODE, VEC, SKEL, SPARSE, false, NV>(a, w, sm, lo, hi, sh, mid, chunk);
     else
-      wfill = main_chunk_v2<HAS_RES, MODE, false, SKEL, SPARSE, false, NV>(a, w, sm, lo, hi, sh, mid, chunk);
+      wfill = main_chunk<HAS_RES, MODE, false, SKEL, SPARSE, false, NV>(a, w, sm, lo, hi, sh, mid, chunk);
     if constexpr (!SKEL) flush_staged<SPARSE && kWritesOut<MODE>>(a, w, sm, lo, hi, sh, mid, wfill);
     (void)wfill;
   }
@@ -1288,7 +973,7 @@ __global__ __launch_bounds__(kMainBlock, 4) void topk_main(StepArgs a, TopkWs w)
   __syncthreads();
   for (int b = tid; b < kHistBins; b += kMainBlock) {
     const uint32_t h = sm.hist[b];
-    if (h) atomicAdd(&w.hist[b * kHistStride], h);
+    if (h) atomicAdd(&w.hist[b], h);
   }
 }
 
@@ -1829,8 +1514,8 @@ __device__ bool finalize_run(const StepArgs& a, const TopkWs& w, int fi, int fcn
      // (agent scope): the parallel fallback below accumulates into this memory with device
      // atomics in the same launch, which a dirty zero line left in some XCD's L2 would overwrite.
      // 16-B sc1 buffer stores: one fabric write per 16 B
-    constexpr int kS4 = kBracketBins * kSampleCopies / 4;
-    constexpr int kZ4 = kS4 + kCoarseBins * kSampleCopies / 4;
+    constexpr int kS4 = kBracketBins / 4;
+    constexpr int kZ4 = kS4 + kCoarseBins / 4;
     const auto rs = __builtin_amdgcn_make_buffer_rsrc(w.shist, (short)0, kS4 * 16, 0x00020000);
     const auto rc = __builtin_amdgcn_make_buffer_rsrc(w.chist, (short)0, (kZ4 - kS4) * 16, 0x00020000);
     typedef float f4v __attribute__((ext_vector_type(4)));
@@ -1857,7 +1542,7 @@ __device__ bool finalize_run(const StepArgs& a, const TopkWs& w, int fi, int fcn
     const int top = kHistBins - 1 - t * PER;
     uint32_t h[PER], sum = 0;
 #pragma unroll
-    for (int j = 0; j < PER; ++j) { h[j] = ld_u32<AG>(&w.hist[(top - j) * kHistStride]); sum += h[j]; }
+    for (int j = 0; j < PER; ++j) { h[j] = ld_u32<AG>(&w.hist[top - j]); sum += h[j]; }
     if (t == 0) { fs.s_B = -1; fs.s_need = 0; }
     const uint32_t ex = block_excl_scan<BLOCK>(sum, fs.s_w, nullptr);
     uint32_t acc = ex;
@@ -2000,10 +1685,7 @@ __global__ __launch_bounds__(256) void topk_all(StepArgs a) {
     emit<MODE>(a, (uint32_t)i, i, compensate<HAS_RES>(a, i));
 }
 
-#ifndef GRACE_MAIN_VEC_NORES_BIG
-#define GRACE_MAIN_VEC_NORES_BIG 64
-#endif
-constexpr int kNoresBigVec = GRACE_MAIN_VEC_NORES_BIG;
+constexpr int kNoresBigVec = 64;
 constexpr int64_t kNoresBigMinN = (int64_t)1024 * kMainBlock * 4 * kNoresBigVec;   // 2^26 at 64
 
 // the main pass at NV float4 per lane per chunk (one chunk per workgroup)
@@ -2050,23 +1732,17 @@ static grace_status_t run_topk(StepArgs a, void* ws, size_t bytes, hipStream_t s
   if (a.stratum < kCarryMinStratum) a.rs_in = a.rs_out = nullptr;   // (grace_topk_carry_size says 0)
   // >= 33 sample workgroups (n > kSmallN): the first two zero the candidate histogram
   static_assert(kSmallN >= kHistBins, "bracket grid covers the histogram zeroing");
-  // runs of kBracketRun samples only when the sample tiles the bucket into whole runs
-  static_assert((kSampleMax / 2) % (kBracketRun * kBracketBlock) == 0, "sample runs tile the grid");
-  if (kBracketRun > 1 && a.sample_n < kSampleMax / 2) {
-    set_error_msg("grace_topk: sample runs need n >= the sample size (A/B build)");
-    return GRACE_ERR_ARG;
-  }
   const bool sparse = kWritesOut<MODE> && a.out && a.prev_idx && a.prev_count > 0;
   if (!sparse) a.prev_idx = nullptr;
   const unsigned nclr = sparse ? (unsigned)min((int64_t)kClearMax, (a.prev_count + kClearPer - 1) / kClearPer) : 0u;
-  topk_bracket<HAS_RES><<<(unsigned)((a.sample_n / kBracketRun + kBracketBlock - 1) / kBracketBlock) + nclr,
+  topk_bracket<HAS_RES><<<(unsigned)((a.sample_n + kBracketBlock - 1) / kBracketBlock) + nclr,
                           kBracketBlock, 0, s>>>(a, w);
   GRACE_CHECK_LAUNCH("topk_bracket");
   bool big = false;
-  if constexpr (!HAS_RES && kMainV3 && kVecOf<HAS_RES, MODE> == GRACE_MAIN_VEC_NORES) {
+  if constexpr (!HAS_RES && kVecOf<HAS_RES, MODE> == kMainVecNoRes) {
     // 4 / 8 B per element (no residual stream): large buckets take chunks of kNoresBigVec float4 per
     // lane, so that the grid is ONE balanced generation (2^26 elements: 1024 workgroups, 4 per CU;
-    // 32 float4 gave 2048 for 1536 resident slots).  r06 A/B (tools/ab_v3.py, 256 MiB, 1 %): main
+    // 32 float4 gave 2048 for 1536 resident slots).  r06 A/B (256 MiB, 1 %): main
     // pass with the recycled output, 32 / 40 / 48 / 64 / 80 / 96 / 128 float4 -> 72.2 / 67.4 / 67.3 /
     // 59.2-60.6 / 69.2 / 72.7 / 58.5 us (820 and 683 workgroups leave CUs unevenly loaded).  Only for
     // k <= n / 50: a wave's LDS region holds 512 flagged elements, ~1.45 % of 16384 at k = 1 %.
@@ -2142,7 +1818,7 @@ __global__ void tag_divide_kernel(const int32_t* idx, int64_t stride, AggCum cum
 //            and written out completely (small_body); a large one gets its sampled bracket
 //            (n/256 samples, 512..2048, into a 32768-bin LDS histogram; the engine's ranks and
 //            thresholds) and its counters / candidate histogram zeroed;
-//   main     one chunk of one large segment per workgroup: the engine's main pass (main_chunk_v2)
+//   main     one chunk of one large segment per workgroup: the engine's main pass (main_chunk)
 //            with that segment's bracket, lists and histogram;
 //   finalize one workgroup per large segment: the engine's finalize (finalize_run) as its own
 //            last arriver -- boundary bin, exact ranking by (|t| desc, index asc), or the
@@ -2150,10 +1826,7 @@ __global__ void tag_divide_kernel(const int32_t* idx, int64_t stride, AggCum cum
 // Payload indices are global (flat-buffer) indices (StepArgs::idx_base = the segment's offset).
 // sample sizes: every sample is two random DRAM reads (g, r), and the bracket launch is bound by
 // their row activations: 8192 per large segment (45 ResNet-50 tensors, 737 K reads) took 47 us
-#ifndef GRACE_SEG_SAMPLE_MAX
-#define GRACE_SEG_SAMPLE_MAX 2048
-#endif
-constexpr int kSegSampleMin = 512, kSegSampleMax = GRACE_SEG_SAMPLE_MAX;
+constexpr int kSegSampleMin = 512, kSegSampleMax = 2048;
 // segments up to this size are selected whole in one prep workgroup (the prep kernel supports up to
 // kSmallN); larger ones take the bracket / main / finalize path.  A 16 K or 32 K segment in one
 // workgroup (four serial rounds of loads, an LDS select over 32 K keys) ended the prep launch
@@ -2301,9 +1974,6 @@ __global__ __launch_bounds__(kSelBlock) void seg_prep_kernel(SegPlan p) {
   static_assert(kBracketBins + kBracketBins / 32 <= kSmallN + 2048, "padded bracket histogram fits the shared block");
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b >= p.nL) {   // a small segment, selected and written completely by this workgroup
-#ifdef GRACE_SEG_NOSMALL   // diagnostic timing build only (small segments left unwritten)
-    return;
-#endif
     const StepArgs a = seg_step_args(p, p.small[b - p.nL]);
     seg_small_body<HAS_RES, MODE>(a, reinterpret_cast<float*>(lds), lds + kSmallN, s_w, s_res);
     return;
@@ -2385,15 +2055,15 @@ __global__ __launch_bounds__(kMainBlock, 4) void seg_main_kernel(SegPlan p) {
   // (no beta = gamma = 1 instantiation here: next to the segment bookkeeping it pushed this kernel
   // to 128 VGPRs and 96 B of scratch per lane)
   if (VEC && (p.seg_off[s] & 3) == 0 && (chunk + 1) * kChunkOf<HAS_RES, MODE> <= a.n) {
-    wfill = main_chunk_v2<HAS_RES, MODE, VEC>(a, w, sm, lo, hi, sh, mid, chunk);
+    wfill = main_chunk<HAS_RES, MODE, VEC>(a, w, sm, lo, hi, sh, mid, chunk);
   } else {
-    wfill = main_chunk_v2<HAS_RES, MODE, false>(a, w, sm, lo, hi, sh, mid, chunk);
+    wfill = main_chunk<HAS_RES, MODE, false>(a, w, sm, lo, hi, sh, mid, chunk);
   }
   flush_staged(a, w, sm, lo, hi, sh, mid, wfill);
   __syncthreads();
   for (int b = tid; b < kHistBins; b += kMainBlock) {
     const uint32_t h = sm.hist[b];
-    if (h) atomicAdd(&w.hist[b * kHistStride], h);
+    if (h) atomicAdd(&w.hist[b], h);
   }
 #ifdef GRACE_STAMPS
   if (tid == 0)
@@ -2768,10 +2438,8 @@ int64_t grace_topk_segmented_carry_len(int64_t n) { return carry_thr_off(seg_sam
 // finalize workgroups for a large segment: one round (kSelBlock * kFinPer candidates) each for the
 // ~2-3 k a segment's small-sample band holds, plus one.  4 k budgeted: at 2 k a second round per
 // workgroup made the largest tensors' routing 8-10 us instead of 3 (ddp_segmented 110.7 -> 106.3 us,
-// profiles/r04_seg_fin_ab.txt).  A/B knob: budget GRACE_SEG_FIN_MULT k
-#ifndef GRACE_SEG_FIN_MULT
-#define GRACE_SEG_FIN_MULT 4
-#endif
+// profiles/r04_seg_fin_ab.txt).
+constexpr int kSegFinMult = 4;
 int64_t grace_topk_segmented_workspace_bytes(const int64_t* sizes, const int64_t* ks, int32_t count) {
   if (!sizes || !ks || count < 0) return -1;
   int64_t total = 0;
@@ -2782,7 +2450,7 @@ int64_t grace_topk_segmented_workspace_bytes(const int64_t* sizes, const int64_t
 
 int32_t grace_topk_segmented_fin_blocks(int64_t n, int64_t k) {
   const int64_t per = (int64_t)kSelBlock * kFinPer;
-  int64_t c = GRACE_SEG_FIN_MULT * k < n ? GRACE_SEG_FIN_MULT * k : n;
+  int64_t c = kSegFinMult * k < n ? kSegFinMult * k : n;
   c = (c + per - 1) / per + 1;
   return (int32_t)(c > kFinBlocks ? kFinBlocks : c);
 }

@@ -1,6 +1,5 @@
 """Diagnostic: the bench's ddp_segmented step (ResNet-50 shapes, world 1) run 40 times for a
-rocprofv3 kernel trace, under whichever library GRACE_HIP_LIB names (A/B and timing-only builds,
-e.g. libgrace_hip_segnosmall.so whose prep leaves the small segments out)."""
+rocprofv3 kernel trace, under whichever library GRACE_HIP_LIB names."""
 import os
 import sys
 

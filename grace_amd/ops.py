@@ -36,6 +36,13 @@ def _p(t):
     return t.data_ptr() if t is not None else None
 
 
+_opt = _p   # the name grace_amd/dist/sharded_terngrad.py calls it by
+
+def seed64(seed):
+    """A seed as the C ABI's uint64 (Python ints are unbounded and may be negative)."""
+    return int(seed) & (2 ** 64 - 1)
+
+
 def dev_f32(t, what="tensor"):
     """Flat, contiguous f32 device view of t (no copy when already so)."""
     if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
@@ -74,40 +81,51 @@ _getrefcount = __import__("sys").getrefcount
 _storage_uses = torch._C._storage_Use_Count
 
 
-def _refcount_selftest():
-    """Whether this interpreter and torch count references the way the output / residual reuse
-    checks assume (only CPython 3.10 / torch 2.10 were exercised).  Replays the exact
-    pattern of OutputRecycler.take -- an entry (tensor, storage cdata, storage) popped from a dict
-    and unpacked -- for a dropped tensor (must read "unheld": refcount 3, storage uses 2), a held one
-    and a held view (both must read "held").  Any other answer turns every reuse path off: the
-    callers then allocate and write densely, exactly as without reuse."""
-    def unheld(d):
-        ent = d.pop("x")
-        buf, cdata, _st = ent
-        return _getrefcount(buf) == 3 and _storage_uses(cdata) == 2
+def park(t, versioned=False):
+    """The entry a cache keeps of a tensor it may hand out again: (t, its storage's cdata, the
+    storage handle, t's version counter or None).  unheld() is the one test on it."""
+    st = t.untyped_storage()
+    return t, st._cdata, st, t._version if versioned else None
 
-    def entry():
+
+def unheld(ent):
+    """Whether nothing outside the cache holds a parked tensor (ent = park(t), still in the cache's
+    dict or just popped from it) or, for a versioned entry, has modified it in place.  Two counts
+    are needed.  The Python object: ent and getrefcount's argument are its only references = 2, so
+    the caller must not have unpacked ent[0] into a name yet.  Its storage, because a view or
+    reshape (``out.view(-1)``, ``out[1:]``) is another tensor on the same storage that the object's
+    refcount cannot see: the StorageImpl use count is 2 exactly when only the parked tensor and the
+    parked storage handle refer to it.  Always false while REUSE_OK is."""
+    return (REUSE_OK and _getrefcount(ent[0]) == 2 and _storage_uses(ent[1]) == 2
+            and (ent[3] is None or ent[0]._version == ent[3]))
+
+
+def _refcount_selftest():
+    """Whether this interpreter and torch count references the way unheld() assumes (VERDICT r4:
+    only CPython 3.10 / torch 2.10 were exercised): park() and unheld() themselves, on an entry
+    left in its dict and on a popped one, must read a dropped tensor "unheld" and a held tensor and
+    a held view "held"; so must the pattern ResidualMemory.spare_for and ShardedTopK's spare
+    residual still spell out (pop, unpack, refcount 3).  Any other answer turns every reuse path
+    off: the callers then allocate and write densely, exactly as without reuse."""
+    def case(hold):
         t = torch.empty(8)
-        st = t.untyped_storage()
-        return t, {"x": (t, st._cdata, st)}
+        d = {"x": park(t, versioned=True)}
+        kept = hold(t)   # noqa: F841  (what the caller still holds, alive until this returns)
+        del t
+        in_dict = unheld(d["x"])
+        ent = d.pop("x")
+        popped = unheld(ent)
+        buf, cdata, _st, _version = ent
+        spelt_out = _getrefcount(buf) == 3 and _storage_uses(cdata) == 2
+        return in_dict + popped + spelt_out   # how many of the three read "unheld"
     try:
-        t, d = entry()
-        del t
-        dropped = unheld(d)
-        t, d = entry()
-        held = unheld(d)
-        t, d = entry()
-        v = t[1:]
-        del t
-        view = unheld(d)
-        del v
-        return dropped and not held and not view
+        return case(lambda t: None) == 3 and case(lambda t: t) == 0 and case(lambda t: t[1:]) == 0
     except Exception:
         return False
 
 
-# every reuse path (reusable_output, OutputRecycler, ResidualMemory.spare_for, ShardedTopK's spare
-# residual) is gated on this
+# every reuse path is gated on this: unheld() reads it, the two sites above read it themselves
+REUSE_OK = True     # open while the self-test runs unheld() itself
 REUSE_OK = _refcount_selftest()
 
 
@@ -128,29 +146,23 @@ def launch_sign_step_w1(x, out):
 def reusable_output(slot, shape, dtype, device):
     """An output tensor for a per-step codec result, reused across calls when nobody outside this
     cache still holds the previous one and the call runs on the stream it was made on, so reuse is
-    stream-ordered behind every earlier use.  "Nobody holds it" needs two checks: the Python object
-    (CPython refcount: tuple + local + argument = 3) and its storage, because a view or reshape
-    (``out.view(-1)``, ``out[1:]``) is another tensor on the same storage that the object's refcount
-    cannot see -- the StorageImpl use count is 2 exactly when only the cached tensor and the cached
-    storage handle refer to it.  A caller that keeps its results, or any view of them, gets a fresh
-    tensor each call, exactly as the reference's new allocations; one that consumes and drops them
-    (``grad.copy_(grc.step(grad, name))``, examples/dist/CIFAR10-dawndist/core.py:204-206) skips
-    the allocator on launch-bound steps."""
+    stream-ordered behind every earlier use (unheld()).  A caller that keeps its results, or any
+    view of them, gets a fresh tensor each call, exactly as the reference's new allocations; one
+    that consumes and drops them (``grad.copy_(grc.step(grad, name))``,
+    examples/dist/CIFAR10-dawndist/core.py:204-206) skips the allocator on launch-bound steps."""
     key = (slot, shape, dtype, device, _stream())
     hit = _reuse.get(key)
-    if hit is not None:
-        buf = hit[0]
-        if REUSE_OK and _getrefcount(buf) == 3 and _storage_uses(hit[1]) == 2:
-            return buf
+    if hit is not None and unheld(hit):
+        return hit[0]
     buf = torch.empty(shape, dtype=dtype, device=device)
-    _reuse[key] = (buf, buf.untyped_storage()._cdata, buf.untyped_storage())
+    _reuse[key] = park(buf)
     return buf
 
 
 class OutputRecycler:
     """Per-name recycled dense outputs of the world-1 top-k step.  A step's result is zero except at
     its payload positions; when the caller has dropped it (no tensor or view of its storage left
-    outside this cache: the reusable_output test) and never modified it (the tensor version counter
+    outside this cache: unheld()) and never modified it (the tensor version counter
     that views share is unchanged), the next step of the same name on the same stream gets it back
     together with the payload indices, and the kernels zero those positions and write only their
     own selection instead of rewriting all n elements (grace_topk_residual_step_carry, prev_idx).
@@ -169,17 +181,13 @@ class OutputRecycler:
         the caller rewrites every element (the buffer is kept for its placement, not to skip
         writes); such hits are counted in dense_hits."""
         numel, device = (like.numel(), like.device) if isinstance(like, torch.Tensor) else (int(like[0]), like[1])
-        hit = self._hit.pop(name, None)
-        if hit is not None:
-            buf, cdata, storage, version, prev_idx, key = hit
-            # references to buf: the popped tuple, the local name, getrefcount's argument
-            if (REUSE_OK and key == (numel, torch.device(device), _stream()) and _getrefcount(buf) == 3
-                    and _storage_uses(cdata) == 2 and buf._version == version):
-                if dense:
-                    self.dense_hits += 1
-                else:
-                    self.hits += 1
-                return buf, prev_idx
+        hit = self._hit.pop(name, None)   # park(out, versioned) + (prev_idx, key)
+        if hit is not None and hit[5] == (numel, torch.device(device), _stream()) and unheld(hit):
+            if dense:
+                self.dense_hits += 1
+            else:
+                self.hits += 1
+            return hit[0], hit[4]
         self.misses += 1
         if not alloc:
             return None, None
@@ -189,8 +197,7 @@ class OutputRecycler:
 
     def keep(self, name, out, idx):
         """Remember this step's result and its payload indices (int32, length k)."""
-        st = out.untyped_storage()
-        self._hit[name] = (out, st._cdata, st, out._version, idx, (out.numel(), out.device, _stream()))
+        self._hit[name] = park(out, versioned=True) + (idx, (out.numel(), out.device, _stream()))
 
     def drop(self, name):
         """Forget `name`'s previous result (its next step allocates and writes densely)."""
@@ -257,7 +264,7 @@ def sign_encode(x, out=None):
 def sign_decode(codes, scale=None):
     codes = require_dev(codes, "codes")
     out = torch.empty(codes.numel(), dtype=F32, device=codes.device)
-    _lib.call("grace_sign_decode", _p(codes), _p(scale) if scale is not None else None, _p(out),
+    _lib.call("grace_sign_decode", _p(codes), _p(scale), _p(out),
               codes.numel(), _stream())
     return out
 
@@ -329,6 +336,24 @@ class TopKWaitError(_lib.GraceNativeError):
     running workgroups have claimed (csrc/topk.hip parallel_exact)."""
 
 
+class StatusWord:
+    """A pinned, device-visible int32 status word that kernels set bits in (system-scope fetch_or)."""
+    __slots__ = ("word", "view")
+
+    def __init__(self):
+        self.word = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+        self.view = self.word.numpy()     # a plain host read per take()
+
+    def data_ptr(self):
+        return self.word.data_ptr()
+
+    def take(self):
+        """Bits set since the last take; never blocks.  A clear word costs no native call; a set one
+        is read and cleared as one host atomic exchange (grace_status_take): a bit a still-running
+        kernel sets between a plain read and a plain clear would be lost."""
+        return int(_lib.query("grace_status_take", self.word.data_ptr())) if self.view[0] else 0
+
+
 _tk_st = None
 
 
@@ -336,20 +361,18 @@ def _topk_status():
     """The pinned word every top-k launch of this process reports a fallback run-out to (registered
     once), checked at every top-k call: it covers the earlier calls whose kernels have finished."""
     global _tk_st
-    hit = _tk_st
-    if hit is None:
-        st = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+    st = _tk_st
+    if st is None:
+        st = StatusWord()
         _lib.call("grace_topk_status_word", st.data_ptr())
-        hit = _tk_st = (st, st.numpy())     # numpy view: a plain host read per call
-    if hit[1][0]:
-        v = int(_lib.query("grace_status_take", hit[0].data_ptr()))   # read-and-clear, host atomic
-        if v & 2:
-            raise TopKWaitError("grace_amd: a top-k exact-fallback wait ran out in an earlier call; its "
-                                "payload, residual and output were not valid -- discard the residual / "
-                                "sharded state of the names stepped since the last check (e.g. "
-                                "memory.residuals.pop(name)), or run with TopKCompressor(check_sync=True) "
-                                "so the failing step itself raises")
-    return hit[0]
+        _tk_st = st
+    if st.take() & 2:
+        raise TopKWaitError("grace_amd: a top-k exact-fallback wait ran out in an earlier call; its "
+                            "payload, residual and output were not valid -- discard the residual / "
+                            "sharded state of the names stepped since the last check (e.g. "
+                            "memory.residuals.pop(name)), or run with TopKCompressor(check_sync=True) "
+                            "so the failing step itself raises")
+    return st
 
 
 def topk_check():
@@ -696,10 +719,6 @@ def seg_tables(sizes, unit, device):
     return hit
 
 
-def _opt(t):
-    return t.data_ptr() if t is not None else None
-
-
 # ----------------------------------------------------------------------------- QSGD
 def qsgd_compress(x, quantum_num, bucket_size, sizes=None, variant=0, u=None, seed=0, norms_in=None, xoff=0,
                   codes_out=None, norms_out=None):
@@ -714,7 +733,7 @@ def qsgd_compress(x, quantum_num, bucket_size, sizes=None, variant=0, u=None, se
                      "qsgd_compress")
     norms = _out_buf(norms_out, nb, F32, x.device, "qsgd_compress norms")
     _lib.call("grace_qsgd_compress_at", _p(x), int(xoff), _p(seg_off), _p(bkt_off), len(sizes), nb, int(quantum_num),
-              int(bucket_size), int(variant), _opt(u), int(seed) & (2 ** 64 - 1), _opt(norms_in), _p(norms),
+              int(bucket_size), int(variant), _p(u), seed64(seed), _p(norms_in), _p(norms),
               _p(codes), _stream())
     return codes, norms
 
@@ -731,7 +750,7 @@ def qsgd_step_w1(x, quantum_num, sizes=None, variant=0, u=None, seed=0):
     seg_off, bkt_off, nb = seg_tables(sizes, 128, x.device)
     out = torch.empty(x.numel(), dtype=F32, device=x.device)
     _lib.call("grace_qsgd_step_w1", _p(x), _p(seg_off), _p(bkt_off), len(sizes), nb, int(quantum_num), int(variant),
-              _opt(u), int(seed) & (2 ** 64 - 1), _p(out), _stream())
+              _p(u), seed64(seed), _p(out), _stream())
     return out
 
 
@@ -770,8 +789,8 @@ def qsgd_global_compress(x, quantum_num, u=None, seed=0, norm_in=None):
     codes = torch.empty(n, dtype=torch.int8 if quantum_num < 128 else torch.float16, device=x.device)
     norm = torch.empty(1, dtype=F32, device=x.device)
     ws = workspace("qsgd_global", _lib.query("grace_qsgd_global_workspace_bytes"), x.device)
-    _lib.call("grace_qsgd_global_compress", _p(x), n, int(quantum_num), _opt(u), int(seed) & (2 ** 64 - 1),
-              _opt(norm_in), _p(norm), _p(codes), _p(ws), _stream())
+    _lib.call("grace_qsgd_global_compress", _p(x), n, int(quantum_num), _p(u), seed64(seed),
+              _p(norm_in), _p(norm), _p(codes), _p(ws), _stream())
     return codes, norm
 
 
@@ -781,16 +800,21 @@ def qsgd_global_decompress(codes, norm, quantum_num, n, world=1, aggregate=False
 
 
 # ----------------------------------------------------------------------------- TernGrad
+def _tern_tables(sizes, n, device):
+    """(sizes, seg_off, unit_off, nunits): the segment table (one tensor of n elements by default)
+    and its device offset tables in TernGrad work units."""
+    sizes = [n] if sizes is None else sizes
+    return (sizes,) + seg_tables(sizes, _lib.query("grace_terngrad_unit"), device)
+
+
 def terngrad_compress(x, sizes=None, clip=None, u=None, seed=0):
     x = dev_f32(x)
-    sizes = [x.numel()] if sizes is None else sizes
-    unit = _lib.query("grace_terngrad_unit")
-    seg_off, unit_off, nunits = seg_tables(sizes, unit, x.device)
+    sizes, seg_off, unit_off, nunits = _tern_tables(sizes, x.numel(), x.device)
     codes = torch.empty(x.numel(), dtype=torch.int8, device=x.device)
     scalars = torch.empty(len(sizes), dtype=F32, device=x.device)
     ws = workspace("terngrad", _lib.query("grace_terngrad_workspace_bytes", nunits), x.device)
-    _lib.call("grace_terngrad_compress", _p(x), _p(seg_off), _p(unit_off), len(sizes), nunits, _opt(clip),
-              _opt(u), int(seed) & (2 ** 64 - 1), _p(codes), _p(scalars), _p(ws), _stream())
+    _lib.call("grace_terngrad_compress", _p(x), _p(seg_off), _p(unit_off), len(sizes), nunits, _p(clip),
+              _p(u), seed64(seed), _p(codes), _p(scalars), _p(ws), _stream())
     return codes, scalars
 
 
@@ -798,14 +822,12 @@ def terngrad_step_w1(x, sizes=None, clip=None, u=None, seed=0):
     """World-1 Allgather(TernGrad).step (grace_terngrad_step_w1): the statistics pass, then one pass
     writing 0 + code * scalar for the codes terngrad_compress would draw, never storing them."""
     x = dev_f32(x)
-    sizes = [x.numel()] if sizes is None else sizes
-    unit = _lib.query("grace_terngrad_unit")
-    seg_off, unit_off, nunits = seg_tables(sizes, unit, x.device)
+    sizes, seg_off, unit_off, nunits = _tern_tables(sizes, x.numel(), x.device)
     scalars = torch.empty(len(sizes), dtype=F32, device=x.device)
     out = torch.empty(x.numel(), dtype=F32, device=x.device)
     ws = workspace("terngrad", _lib.query("grace_terngrad_workspace_bytes", nunits), x.device)
-    _lib.call("grace_terngrad_step_w1", _p(x), _p(seg_off), _p(unit_off), len(sizes), nunits, _opt(clip),
-              _opt(u), int(seed) & (2 ** 64 - 1), _p(scalars), _p(ws), _p(out), _stream())
+    _lib.call("grace_terngrad_step_w1", _p(x), _p(seg_off), _p(unit_off), len(sizes), nunits, _p(clip),
+              _p(u), seed64(seed), _p(scalars), _p(ws), _p(out), _stream())
     return out
 
 
@@ -814,9 +836,7 @@ def terngrad_decompress_records(records, rec_bytes, world, rank_lo, packed, scal
     (grace_terngrad_decompress_records): int8 codes, or 2-bit planar packed (packed=True);
     rank_lo: device int64[W + 1], each rank's element range boundaries."""
     records, scalars = require_dev(records), require_dev(scalars)
-    sizes = [n] if sizes is None else sizes
-    unit = _lib.query("grace_terngrad_unit")
-    seg_off, _, _ = seg_tables(sizes, unit, records.device)
+    sizes, seg_off, _, _ = _tern_tables(sizes, n, records.device)
     out = torch.empty(n, dtype=F32, device=records.device)
     _lib.call("grace_terngrad_decompress_records", _p(records), int(rec_bytes), int(world), _p(rank_lo),
               1 if packed else 0, _p(scalars), _p(seg_off), len(sizes), int(n), _p(out), _stream())
@@ -825,9 +845,7 @@ def terngrad_decompress_records(records, rec_bytes, world, rank_lo, packed, scal
 
 def terngrad_decompress(codes, scalars, n, sizes=None, world=1, aggregate=False, divisor=1.0):
     codes, scalars = require_dev(codes), require_dev(scalars)
-    sizes = [n] if sizes is None else sizes
-    unit = _lib.query("grace_terngrad_unit")
-    seg_off, _, _ = seg_tables(sizes, unit, codes.device)
+    sizes, seg_off, _, _ = _tern_tables(sizes, n, codes.device)
     out = torch.empty(n, dtype=F32, device=codes.device)
     _lib.call("grace_terngrad_decompress", _p(codes), _p(scalars), n, len(sizes), int(world), _p(seg_off),
               len(sizes), n, 1 if aggregate else 0, float(divisor), _p(out), _stream())
@@ -839,7 +857,7 @@ def natural_compress(x, rand_int=None, seed=0, xoff=0, out=None):
     """xoff (a multiple of 4): the element of a larger bucket x[0] is, for the device generator."""
     x = dev_f32(x)
     codes = _out_buf(out, x.numel(), torch.uint8, x.device, "natural_compress")
-    _lib.call("grace_natural_compress_at", _p(x), int(xoff), x.numel(), _opt(rand_int), int(seed) & (2 ** 64 - 1),
+    _lib.call("grace_natural_compress_at", _p(x), int(xoff), x.numel(), _p(rand_int), seed64(seed),
               _p(codes), _stream())
     return codes
 
@@ -848,8 +866,8 @@ def cnat_compress(x, rand=None, deterministic=False, seed=0, xoff=0, out=None):
     """xoff (a multiple of 4): the element of a larger bucket x[0] is, for the device generator."""
     x = dev_f32(x)
     codes = _out_buf(out, x.numel(), torch.uint8, x.device, "cnat_compress")
-    _lib.call("grace_cnat_compress_at", _p(x), int(xoff), x.numel(), _opt(rand), 1 if deterministic else 0,
-              int(seed) & (2 ** 64 - 1), _p(codes), _stream())
+    _lib.call("grace_cnat_compress_at", _p(x), int(xoff), x.numel(), _p(rand), 1 if deterministic else 0,
+              seed64(seed), _p(codes), _stream())
     return codes
 
 
@@ -889,7 +907,7 @@ def cast_step_w1(x, mode, seed):
     """grace_cast_step_w1: out = 0 + decompress(compress(x)) for natural (0), cnat (1), cnat
     deterministic (2) or fp16 (3), in one pass; same shape as x."""
     out = torch.empty_like(x)
-    _lib.call("grace_cast_step_w1", _p(x), x.numel(), int(mode), int(seed) & (2 ** 64 - 1), _p(out), _stream())
+    _lib.call("grace_cast_step_w1", _p(x), x.numel(), int(mode), seed64(seed), _p(out), _stream())
     return out
 
 
@@ -919,14 +937,14 @@ def rank_of_process():
 # ----------------------------------------------------------------------------- random-k / threshold
 def randomk_indices(seed, numel, k, device):
     idx = torch.empty(k, dtype=torch.int64, device=device)
-    _lib.call("grace_randomk_indices", int(seed) & (2 ** 64 - 1), int(numel), int(k), _p(idx), _stream())
+    _lib.call("grace_randomk_indices", seed64(seed), int(numel), int(k), _p(idx), _stream())
     return idx
 
 
 def randomk_perm_indices(seed, numel, k, device):
     """k distinct indices of [0, numel) (Horovod-flavour randperm(numel)[:k] semantics)."""
     idx = torch.empty(k, dtype=torch.int64, device=device)
-    _lib.call("grace_randomk_perm_indices", int(seed) & (2 ** 64 - 1), int(numel), int(k), _p(idx), _stream())
+    _lib.call("grace_randomk_perm_indices", seed64(seed), int(numel), int(k), _p(idx), _stream())
     return idx
 
 
@@ -1055,7 +1073,7 @@ def powersgd_p_draw(M2d, r, seed, out=None):
     n, m = M2d.shape
     P = _out_buf(out.reshape(-1) if out is not None else None, n * r, F32, M2d.device, "powersgd_p_draw").view(n, r)
     ws = workspace("powersgd", _lib.query("grace_powersgd_workspace_bytes", n, m, r), M2d.device)
-    _lib.call("grace_powersgd_p_draw", _p(M2d), n, m, int(seed) & (2 ** 64 - 1), int(r), _p(P), _p(ws), _stream())
+    _lib.call("grace_powersgd_p_draw", _p(M2d), n, m, seed64(seed), int(r), _p(P), _p(ws), _stream())
     return P
 
 
@@ -1086,7 +1104,7 @@ def powersgd_w1_compress(M2d, q=None, seed=0):
     status = _w1_status(dev)
     _w1_order(dev)
     _lib.call("grace_powersgd_w1_compress", _p(M2d), n, m, _p(require_dev(q)) if q is not None else None,
-              int(seed) & (2 ** 64 - 1), _p(P), _p(Q), _p(ws), ws.numel(), status.data_ptr(), _stream())
+              seed64(seed), _p(P), _p(Q), _p(ws), ws.numel(), status.data_ptr(), _stream())
     return P, Q
 
 
@@ -1121,19 +1139,13 @@ def _w1_status(dev):
     here at every call: it covers the earlier calls whose kernels have finished since.  Bit 1 (a
     wait ran out: that call's P and Q were not valid) raises PowerSGDWaitError."""
     key = str(dev)
-    hit = _w1_st.get(key)
-    if hit is None:
-        st = torch.zeros(1, dtype=torch.int32, pin_memory=True)
-        hit = _w1_st[key] = (st, st.numpy())     # numpy view: a plain host read per call
-    st, view = hit
-    if view[0]:
-        # read-and-clear as one host atomic exchange: a bit a still-running kernel sets between a
-        # plain read and a plain clear would be lost
-        v = int(_lib.query("grace_status_take", st.data_ptr()))
-        if v & 2:
-            raise PowerSGDWaitError("grace_amd: a one-pass PowerSGD wait ran out in an earlier call; its P and Q "
-                                    "were not valid (never expected: another kernel kept its workgroups from "
-                                    "becoming resident)")
+    st = _w1_st.get(key)
+    if st is None:
+        st = _w1_st[key] = StatusWord()
+    if st.take() & 2:
+        raise PowerSGDWaitError("grace_amd: a one-pass PowerSGD wait ran out in an earlier call; its P and Q "
+                                "were not valid (never expected: another kernel kept its workgroups from "
+                                "becoming resident)")
     return st
 
 
@@ -1157,7 +1169,7 @@ def orthogonalize_(A):
 def normal_orthogonal(shape, seed, device):
     """orthogonalize(normal draws of `shape`) in one launch (draws as ops.normal)."""
     A = torch.empty(shape, dtype=F32, device=device)
-    _lib.call("grace_normal_orthogonal", _p(A), shape[0], shape[1], int(seed) & (2 ** 64 - 1), _stream())
+    _lib.call("grace_normal_orthogonal", _p(A), shape[0], shape[1], seed64(seed), _stream())
     return A
 
 
@@ -1167,14 +1179,13 @@ def powersgd_outer(P, Q, M2d=None, want_out=True, want_residual=False):
     dev = P.device
     out = torch.empty(n, m, dtype=F32, device=dev) if want_out else None
     res = torch.empty(n, m, dtype=F32, device=dev) if want_residual else None
-    _lib.call("grace_powersgd_outer", _p(P), _p(Q), n, m, r, _p(out) if out is not None else None,
-              _p(M2d) if M2d is not None else None, _p(res) if res is not None else None, _stream())
+    _lib.call("grace_powersgd_outer", _p(P), _p(Q), n, m, r, _p(out), _p(M2d), _p(res), _stream())
     return out, res
 
 
 def normal(shape, seed, device):
     x = torch.empty(shape, dtype=F32, device=device)
-    _lib.call("grace_normal_fill", _p(x), x.numel(), int(seed) & (2 ** 64 - 1), _stream())
+    _lib.call("grace_normal_fill", _p(x), x.numel(), seed64(seed), _stream())
     return x
 
 
@@ -1198,7 +1209,7 @@ def shard_select(recs, world, rank, cap, tab, k, residual, out, out_base, pay_id
         raise ValueError("shard_select: sel_gi must be int32 with world * cap elements")
     ws = workspace("shardsel", _lib.query("grace_shard_select_workspace_bytes", int(world), int(cap)), dev)
     _lib.call("grace_shard_select", _p(recs), int(world), int(rank), int(cap), _p(tab), int(k), _p(residual),
-              _p(out), int(out_base), out.numel(), _p(pay_idx), _opt(sel_gi), _p(ws), ws.numel(), status.data_ptr(),
+              _p(out), int(out_base), out.numel(), _p(pay_idx), _p(sel_gi), _p(ws), ws.numel(), status.data_ptr(),
               _stream())
 
 
@@ -1209,13 +1220,13 @@ def shard_clear(out, out_base, sel_gi):
 
 
 def new_status_word():
-    """A pinned, device-visible int32 status word that kernels set bits in (system-scope fetch_or)."""
-    return torch.zeros(1, dtype=torch.int32, pin_memory=True)
+    """A fresh StatusWord (what ShardedTopK and grace_shard_select's callers pass as `status`)."""
+    return StatusWord()
 
 
 def status_take(st):
-    """Bits set in a pinned status word since the last take (host atomic exchange; never blocks)."""
-    return int(_lib.query("grace_status_take", st.data_ptr())) if int(st[0]) else 0
+    """Bits set in a StatusWord since the last take (never blocks)."""
+    return st.take()
 
 
 # ----------------------------------------------------------------------------- DGC
@@ -1246,19 +1257,31 @@ def _dgc_sample_top(sample, ks):
     return top, ks
 
 
+def _dgc_sample_top_of(t, ratio, sample_idx, seed, state=None):
+    """The sampling prelude of every DGC entry: draw the 1 % sample of flat t (grace_dgc_sample) --
+    or, with state = (residual, accum, has_state, momentum), of the gradient t compensated from
+    that memory (grace_dgc_sample_comp) -- and take its top by _dgc_sample_top."""
+    n = t.numel()
+    ns = max(1, int(n * 0.01))
+    ks = max(1, int(n * ratio * 0.01))
+    sample = torch.empty(ns, dtype=F32, device=t.device)
+    if state is None:
+        _lib.call("grace_dgc_sample", _p(t), n, _p(sample_idx), seed64(seed), ns, _p(sample), _stream())
+    else:
+        residual, accum, has_state, momentum = state
+        _lib.call("grace_dgc_sample_comp", _p(t), _p(residual) if has_state else None,
+                  _p(accum) if has_state else None, 1 if has_state else 0, float(momentum), n, _p(sample_idx),
+                  seed64(seed), ns, _p(sample), _stream())
+    return _dgc_sample_top(sample, min(ks, ns))
+
+
 def dgc_compress(t, ratio, sample_idx=None, seed=0):
     """DgcCompressor.compress (dgc.py:12-43) of flat t: (values f32, indices int64, meta) where
     meta (16 B, device) holds the final threshold for dgc_mask_update.  sample_idx: int64 device
     indices (the reference's CPU uniform_ stream) or None for the device generator."""
     t = dev_f32(t)
     n = t.numel()
-    ns = max(1, int(n * 0.01))
-    ks = max(1, int(n * ratio * 0.01))
-    sample = torch.empty(ns, dtype=F32, device=t.device)
-    _lib.call("grace_dgc_sample", _p(t), n, _opt(sample_idx), int(seed) & (2 ** 64 - 1), ns, _p(sample), _stream())
-    top, kt = _dgc_sample_top(sample, min(ks, ns))
-    ws = workspace("dgc", _lib.query("grace_dgc_workspace_bytes", n), t.device)
-    _lib.call("grace_dgc_threshold", _p(t), n, _p(top), kt, float(ratio), _p(ws), _stream())
+    ws = _dgc_threshold(t, ratio, sample_idx, seed, "grace_dgc_threshold")
     meta = ws[:16].clone()
     count = int(meta[8:12].view(torch.int32).item())          # host sync: the payload size
     vals = torch.empty(count, dtype=F32, device=t.device)
@@ -1268,20 +1291,21 @@ def dgc_compress(t, ratio, sample_idx=None, seed=0):
     return vals, idx, meta
 
 
+def _dgc_threshold(t, ratio, sample_idx, seed, native):
+    """The sample's top, then `native` (grace_dgc_threshold or grace_dgc_select) over flat t into
+    the DGC workspace, which is returned."""
+    n = t.numel()
+    top, kt = _dgc_sample_top_of(t, ratio, sample_idx, seed)
+    ws = workspace("dgc", _lib.query("grace_dgc_workspace_bytes", n), t.device)
+    _lib.call(native, _p(t), n, _p(top), kt, float(ratio), _p(ws), _stream())
+    return ws
+
+
 def dgc_threshold_dev(t, ratio, sample_idx=None, seed=0):
     """DgcCompressor.compress's threshold, chunk counts and offsets (grace_dgc_threshold) with NO
     host read: the count stays on the device (meta words: thr0, thr, count at ws[8:12]) for the
     capacity-bounded or counts exchange (grace_amd/dist/compressor/dgc.py)."""
-    t = dev_f32(t)
-    n = t.numel()
-    ns = max(1, int(n * 0.01))
-    ks = max(1, int(n * ratio * 0.01))
-    sample = torch.empty(ns, dtype=F32, device=t.device)
-    _lib.call("grace_dgc_sample", _p(t), n, _opt(sample_idx), int(seed) & (2 ** 64 - 1), ns, _p(sample), _stream())
-    top, kt = _dgc_sample_top(sample, min(ks, ns))
-    ws = workspace("dgc", _lib.query("grace_dgc_workspace_bytes", n), t.device)
-    _lib.call("grace_dgc_threshold", _p(t), n, _p(top), kt, float(ratio), _p(ws), _stream())
-    return ws
+    return _dgc_threshold(dev_f32(t), ratio, sample_idx, seed, "grace_dgc_threshold")
 
 
 def dgc_write_capped(t, ws, cap):
@@ -1299,16 +1323,7 @@ def dgc_mask_update_capped(rec, cap, residual, accum):
 def dgc_select(t, ratio, sample_idx=None, seed=0):
     """The sampled threshold and its adjustment loop only (grace_dgc_select); returns the DGC
     workspace whose first 16 bytes are the meta grace_dgc_step_w1 / dgc_mask_update read."""
-    t = dev_f32(t)
-    n = t.numel()
-    ns = max(1, int(n * 0.01))
-    ks = max(1, int(n * ratio * 0.01))
-    sample = torch.empty(ns, dtype=F32, device=t.device)
-    _lib.call("grace_dgc_sample", _p(t), n, _opt(sample_idx), int(seed) & (2 ** 64 - 1), ns, _p(sample), _stream())
-    top, kt = _dgc_sample_top(sample, min(ks, ns))
-    ws = workspace("dgc", _lib.query("grace_dgc_workspace_bytes", n), t.device)
-    _lib.call("grace_dgc_select", _p(t), n, _p(top), kt, float(ratio), _p(ws), _stream())
-    return ws
+    return _dgc_threshold(dev_f32(t), ratio, sample_idx, seed, "grace_dgc_select")
 
 
 def dgc_step_w1(t, residual, accum, ws, out=None):
@@ -1324,13 +1339,7 @@ def dgc_step_w1_fused(g, residual, accum, has_state, momentum, ratio, sample_idx
     read.  Same values as compensate + select + step_w1."""
     g = dev_f32(g)
     n = g.numel()
-    ns = max(1, int(n * 0.01))
-    ks = max(1, int(n * ratio * 0.01))
-    sample = torch.empty(ns, dtype=F32, device=g.device)
-    _lib.call("grace_dgc_sample_comp", _p(g), _p(residual) if has_state else None,
-              _p(accum) if has_state else None, 1 if has_state else 0, float(momentum), n, _opt(sample_idx),
-              int(seed) & (2 ** 64 - 1), ns, _p(sample), _stream())
-    top, kt = _dgc_sample_top(sample, min(ks, ns))
+    top, kt = _dgc_sample_top_of(g, ratio, sample_idx, seed, state=(residual, accum, has_state, momentum))
     ws = workspace("dgc_w1", _lib.query("grace_dgc_step_w1_fused_workspace_bytes", n), g.device)
     r_new, a_new, out = torch.empty_like(g), torch.empty_like(g), torch.empty_like(g)
     _lib.call("grace_dgc_step_w1_fused", _p(g), _p(residual) if has_state else None,

@@ -184,7 +184,7 @@ def test_w1_status_word_raises():
     M = _t(np.random.default_rng(2).standard_normal((512, 256)).astype(np.float32))
     ops.powersgd_w1_compress(M)
     torch.cuda.synchronize()
-    st, view = ops._w1_st[str(M.device)]
+    view = ops._w1_st[str(M.device)].view
     view[0] = 2
     with pytest.raises(ops.PowerSGDWaitError):
         ops.powersgd_w1_compress(M)

@@ -74,8 +74,9 @@ def test_other_name_size_or_stream_allocates(_cpu_stream):
 
 def test_refcount_model_selftest_and_gate(monkeypatch):
     """the reuse checks rest on CPython / torch reference counts.  The import-time
-    self-test replays their exact pattern and must accept this interpreter; with the gate off
-    (as it would be on an interpreter that counts differently) nothing is ever handed back."""
+    self-test runs ops.park / ops.unheld themselves, and the pattern the residual memories still
+    spell out, and must accept this interpreter; with the gate off (as it would be on an
+    interpreter that counts differently) nothing is ever handed back."""
     assert ops._refcount_selftest() and ops.REUSE_OK
     monkeypatch.setattr(ops, "REUSE_OK", False)
     rec = ops.OutputRecycler()
@@ -108,3 +109,49 @@ def test_residual_spare_buffer_respects_holders():
     del c
     d = mem.spare_for("w", like)
     assert d.data_ptr() != v.data_ptr() - 12      # a view held: a fresh buffer
+
+
+def test_reusable_output_respects_holders_and_stream(_cpu_stream):
+    """ops.reusable_output (the launch-bound sign step's output) on CPU tensors: a dropped result
+    comes back; a held result, a held view of it, or a call on another stream gets a fresh tensor."""
+    def get():
+        return ops.reusable_output("test_holders", (4, 8), torch.float32, torch.device("cpu"))
+    out = get()
+    p = out.data_ptr()
+    del out
+    out = get()
+    assert out.data_ptr() == p and out.shape == (4, 8)      # dropped: reused
+    new = get()                                             # `out` is held
+    assert new.data_ptr() != out.data_ptr()
+    view = new[1:]
+    del new
+    new = get()                                             # a view of the cached tensor is held
+    assert new.data_ptr() != view.data_ptr() - 32
+    p = new.data_ptr()
+    del new, view
+    _cpu_stream["s"] = 7
+    other = get()                                           # another stream: its own buffer
+    assert other.data_ptr() != p
+    _cpu_stream["s"] = 0
+    assert get().data_ptr() == p                            # the first stream's is still parked
+
+
+@pytest.mark.parametrize("ok", [True, False])
+def test_gate_covers_reusable_output_and_residual_spare(monkeypatch, ok):
+    """REUSE_OK off turns off every reuse path, not only OutputRecycler (above): with it on a
+    dropped buffer comes back, with it off the caller gets a fresh one.  (ShardedTopK's spare
+    residual: tests/test_sharded_gloo.py.)"""
+    from grace_amd.dist.memory.residual import ResidualMemory
+    monkeypatch.setattr(ops, "REUSE_OK", ok)
+    out = ops.reusable_output("test_gate", (16,), torch.float32, torch.device("cpu"))
+    p = out.data_ptr()
+    del out
+    out = ops.reusable_output("test_gate", (16,), torch.float32, torch.device("cpu"))
+    assert (out.data_ptr() == p) == ok
+    mem = ResidualMemory()
+    like = torch.empty(64)
+    a = mem.spare_for("w", like)
+    mem.retire("w", a)
+    p = a.data_ptr()
+    del a
+    assert (mem.spare_for("w", like).data_ptr() == p) == ok

@@ -231,3 +231,35 @@ def test_sharded_resize_reported_at_the_same_step_on_every_rank():
     shrinks at step 1; both ranks raise at step 3."""
     outs = _run(2, [40000, 40000], "normal", 0.01, sizes2=[40000, 25000], steps=6)
     assert [int(o["raised_at"][0]) for o in outs] == [3, 3]
+
+
+def _w1_steps(eng, steps, n=4000):
+    """`steps` steps of one name at world 1 (no process group), the emulator kernels on CPU tensors"""
+    for s in range(steps):
+        eng.step(torch.from_numpy(_bucket("normal", n, 200 + s)), "b")
+
+
+@pytest.mark.parametrize("ok", [True, False])
+def test_spare_residual_is_reused_only_with_the_gate_open(monkeypatch, ok):
+    """A step writes its residual into the buffer the name had before the current one when the
+    caller dropped it (step 3 gets step 1's back); with ops.REUSE_OK off it allocates."""
+    from grace_amd import ops
+    from grace_amd.dist.sharded import ShardedTopK
+    monkeypatch.setattr(ops, "REUSE_OK", ok)
+    eng = ShardedTopK(0.01, kernels=OracleShardKernels())
+    _w1_steps(eng, 1)
+    first = eng.residuals["b"].data_ptr()
+    _w1_steps(eng, 2)
+    assert (eng.residuals["b"].data_ptr() == first) == ok
+
+
+def test_held_residual_is_never_taken_as_the_spare():
+    """The caller keeps step 1's residual: two steps later it is the name's spare, still held, so
+    step 3 must not write into it."""
+    from grace_amd.dist.sharded import ShardedTopK
+    eng = ShardedTopK(0.01, kernels=OracleShardKernels())
+    _w1_steps(eng, 1)
+    kept = eng.residuals["b"]
+    before = kept.clone()
+    _w1_steps(eng, 2)
+    assert torch.equal(kept, before) and eng.residuals["b"].data_ptr() != kept.data_ptr()

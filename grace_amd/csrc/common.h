@@ -63,6 +63,20 @@ __device__ __forceinline__ float u2f(uint32_t x) { return __uint_as_float(x); }
 // Ordering key of |x|: monotone in |x|; NaN above +inf; -0 == +0.
 __device__ __forceinline__ uint32_t abs_key(float x) { return f2u(x) & 0x7FFFFFFFu; }
 
+// bfloat16 travels as its 16 bits (uint16_t).  Widening is exact; narrowing rounds to nearest even
+// in integer arithmetic, so subnormals are rounded, not flushed, and the result is bit for bit
+// torch's CPU `.to(torch.bfloat16)` (a NaN becomes the quiet NaN 0x7FC0).
+__device__ __forceinline__ float bf16_to_f32(uint16_t b) { return u2f((uint32_t)b << 16); }
+__device__ __forceinline__ uint16_t f32_to_bf16(float x) {
+  const uint32_t u = f2u(x);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)0x7FC0u;
+  return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+// two results as one 32-bit word (element 0 in the low half: little-endian bf16 pairs)
+__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
+  return (uint32_t)f32_to_bf16(a) | ((uint32_t)f32_to_bf16(b) << 16);
+}
+
 // Lane's position among the set lanes of a 64-bit ballot mask (v_mbcnt_lo/hi).
 __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));

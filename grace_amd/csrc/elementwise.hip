@@ -92,6 +92,16 @@ struct AccOp {
   __device__ void one(int64_t i) const { acc[i] = (first ? 0.f : acc[i]) + x[i]; }
 };
 
+// f32 -> bf16, round to nearest even (common.h f32_to_bf16): 16 B read, 8 B written per quad
+struct Bf16Op {
+  const float* x; uint16_t* o;
+  __device__ void vec(int64_t i) const {
+    const float4 v = reinterpret_cast<const float4*>(x)[i];
+    reinterpret_cast<uint2*>(o)[i] = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
+  }
+  __device__ void one(int64_t i) const { o[i] = f32_to_bf16(x[i]); }
+};
+
 __device__ __forceinline__ uint32_t pack_ge0(float4 x) {
   return (uint32_t)(x.x >= 0.f) | ((uint32_t)(x.y >= 0.f) << 8) | ((uint32_t)(x.z >= 0.f) << 16) |
          ((uint32_t)(x.w >= 0.f) << 24);
@@ -430,6 +440,12 @@ grace_status_t grace_div_scalar(const float* x, float divisor, float* out, int64
   GRACE_REQUIRE(n >= 0 && x && out, "grace_div_scalar: bad arguments");
   return launch_stream("grace_div_scalar", DivOp{x, divisor, out}, n, aligned16(x) && aligned16(out),
                        stream);
+}
+
+grace_status_t grace_f32_to_bf16(const float* x, uint16_t* out, int64_t n, void* stream) {
+  GRACE_REQUIRE(n >= 0 && x && out, "grace_f32_to_bf16: bad arguments");
+  return launch_stream("grace_f32_to_bf16", Bf16Op{x, out}, n,
+                       aligned16(x) && (reinterpret_cast<uintptr_t>(out) & 7u) == 0, stream);
 }
 
 int64_t grace_hbm_probe_elems(int64_t n, int32_t variant) {

@@ -68,12 +68,32 @@ constexpr int kMainVecNoRes = 32;                          // ... and at 4 / 8 B
 //   12 B (g, r read; r' written; world > 1): 12288 / 16384 / 20480 -> 217-221 / 208-212 / 206 us;
 //    8 B (no residual stream; no memory or a first step): 16384 -> 132, 32768 -> 107 us;
 //        24576 / 28672 / 40960 -> 116 / 114 / 112 us.
-template <bool HAS_RES, int MODE>
-constexpr int kBytesOf = 4 + (HAS_RES ? 4 : 0) + (kWritesR<MODE> ? 4 : 0) + (kWritesOut<MODE> ? 4 : 0);
-template <bool HAS_RES, int MODE>
-constexpr int kVecOf = kBytesOf<HAS_RES, MODE> >= 16 ? kMainVec
+//
+// E: the element type of the gradient and of the dense output -- float, or bfloat16 carried as its
+// bits (uint16_t; the residual, the payload, the carry and every list stay f32 / int).  StepArgs
+// declares g and out as float pointers; the uint16_t instantiations read them through g_of<E> /
+// out_of<E>, so the f32 kernels' argument block and code are what they were before E existed.
+// bf16 moves 2 B for g and for out: 2 / 4 / 6 / 8 B per element without a residual stream, 10 B
+// (g, r read; r' written) and 12 B (and out written) with one.  The chunk is taken from the measured
+// classes above by the streams a lane keeps in flight, not re-tuned: 32 float4 per lane without a
+// residual stream (the 4 / 8 B class), 20 with one (the 12 B class, which also serves the 10 B pass).
+template <typename E> constexpr bool kIsBf16 = sizeof(E) == 2;
+template <bool HAS_RES, int MODE, typename E = float>
+constexpr int kBytesOf = (int)sizeof(E) + (HAS_RES ? 4 : 0) + (kWritesR<MODE> ? 4 : 0) +
+                         (kWritesOut<MODE> ? (int)sizeof(E) : 0);
+template <bool HAS_RES, int MODE, typename E = float>
+constexpr int kVecOf = kIsBf16<E> ? (HAS_RES ? kMainVec12B : kMainVecNoRes)
+                       : kBytesOf<HAS_RES, MODE> >= 16 ? kMainVec
                        : (kBytesOf<HAS_RES, MODE> >= 12 ? kMainVec12B : kMainVecNoRes);
+// (f32 only: its users -- the segmented kernels, the stream probe, grace_topk_segmented_chunk -- have
+// no bf16 form; a bf16 pass's chunk is kMainBlock * 4 * kVecOf<HAS_RES, MODE, E>, in run_topk)
 template <bool HAS_RES, int MODE> constexpr int kChunkOf = kMainBlock * 4 * kVecOf<HAS_RES, MODE>;
+// bf16 world-1 residual step (kDenseFused): the f32 pass parks t of a provisional pick in `out` and
+// writes r' = t - t at once, and its exact fallback reads t back from there.  A bf16 `out` holds t
+// rounded, so this pass leaves t in r everywhere (as kDenseRes does) and the finalize zeroes the k
+// selected positions of r; `out` is still written provisionally and fixed up.
+template <int MODE, typename E>
+constexpr bool kRKeepsT = MODE == kDenseRes || (MODE == kDenseFused && kIsBf16<E>);
 // (r05 A/B at BASELINE configs[4]'s 8.4 M-element shard, 12 B per element: 410 chunks of 20480
 // leave CUs with 1-2 workgroups, yet chunks of 16384 (512, two per CU) or 12288 (683) ran the local
 // step in 57.5-58.4 / 59.2-60.3 us against 57.3-57.4 -- the small bucket's main pass is bound by
@@ -309,10 +329,59 @@ constexpr int64_t kCarryMinStratum = 256;
 // sample count n / 256 can be odd)
 __host__ __device__ __forceinline__ int64_t carry_thr_off(int64_t S) { return (S + 1) & ~(int64_t)1; }
 
-template <bool HAS_RES>
+// the gradient and the dense output as the element type E of the instantiation (kBytesOf)
+template <typename E>
+__device__ __forceinline__ const E* g_of(const StepArgs& a) { return reinterpret_cast<const E*>(a.g); }
+template <typename E>
+__device__ __forceinline__ E* out_of(const StepArgs& a) { return reinterpret_cast<E*>(a.out); }
+// one element widened to f32 / one f32 result narrowed (round to nearest even) and stored
+template <typename E>
+__device__ __forceinline__ float ld_elem(const E* p, int64_t i) {
+  if constexpr (kIsBf16<E>) return bf16_to_f32(p[i]);
+  else return p[i];
+}
+template <typename E>
+__device__ __forceinline__ void st_elem(E* p, int64_t i, float v) {
+  if constexpr (kIsBf16<E>) p[i] = f32_to_bf16(v);
+  else p[i] = v;
+}
+// four consecutive elements with plain (cached) accesses: p + i aligned to 4 elements
+template <typename E>
+__device__ __forceinline__ float4 ld_quad(const E* p, int64_t i) {
+  if constexpr (kIsBf16<E>) {
+    const uint2 w = *reinterpret_cast<const uint2*>(p + i);
+    return make_float4(u2f(w.x << 16), u2f(w.x & 0xFFFF0000u), u2f(w.y << 16), u2f(w.y & 0xFFFF0000u));
+  } else {
+    return *reinterpret_cast<const float4*>(p + i);
+  }
+}
+template <typename E>
+__device__ __forceinline__ void st_quad(E* p, int64_t i, float4 v) {
+  if constexpr (kIsBf16<E>) *reinterpret_cast<uint2*>(p + i) = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
+  else *reinterpret_cast<float4*>(p + i) = v;
+}
+// whether the vector paths may run: 4 elements of every stream per aligned access (16 B of f32,
+// 8 B of bf16; the residual is always f32)
+template <typename E>
+__host__ __device__ __forceinline__ bool quad_aligned(const StepArgs& a) {
+  if constexpr (kIsBf16<E>)
+    return ((reinterpret_cast<uintptr_t>(a.r) & 15u) |
+            ((reinterpret_cast<uintptr_t>(a.g) | reinterpret_cast<uintptr_t>(a.out)) & 7u)) == 0;
+  else
+    return ((reinterpret_cast<uintptr_t>(a.g) | reinterpret_cast<uintptr_t>(a.r) |
+             reinterpret_cast<uintptr_t>(a.out)) & 15u) == 0;
+}
+
+template <bool HAS_RES, typename E = float>
 __device__ __forceinline__ float compensate(const StepArgs& a, int64_t i) {
-  if constexpr (HAS_RES) return a.beta * a.r_in[i] + a.gamma * a.g[i];
-  return a.g[i];
+  if constexpr (kIsBf16<E>) {
+    const float gv = bf16_to_f32(g_of<E>(a)[i]);
+    if constexpr (HAS_RES) return a.beta * a.r_in[i] + a.gamma * gv;
+    return gv;
+  } else {
+    if constexpr (HAS_RES) return a.beta * a.r_in[i] + a.gamma * a.g[i];
+    return a.g[i];
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -501,7 +570,7 @@ __device__ __forceinline__ void clear_prev(const StepArgs& a, unsigned b, unsign
 constexpr int kClearPer = kBracketBlock * 8;   // previous-payload entries per clear workgroup and round
 constexpr int kClearMax = 96;                   // clear workgroups at most
 
-template <bool HAS_RES>
+template <bool HAS_RES, typename E = float>
 __global__ __launch_bounds__(kBracketBlock) void topk_bracket(StepArgs a, TopkWs w) {
   // workgroups past the sample grid clear the recycled output (no ticket: not part of the sample)
   const unsigned nsamp = (unsigned)((a.sample_n + kBracketBlock - 1) / kBracketBlock);
@@ -532,11 +601,11 @@ __global__ __launch_bounds__(kBracketBlock) void topk_bracket(StepArgs a, TopkWs
       // sample instead of two
       const float tp = a.rs_in[sidx];
       const uint64_t Tp = *reinterpret_cast<const uint64_t*>(a.rs_in + carry_thr_off(a.sample_n));
-      const float gv = a.g[pos];
+      const float gv = ld_elem(g_of<E>(a), pos);
       const float rp = comp_key(abs_key(tp), (uint32_t)pos) >= Tp ? tp - tp : tp;
       t[0] = a.beta * rp + a.gamma * gv;
     } else {
-      t[0] = compensate<HAS_RES>(a, pos);
+      t[0] = compensate<HAS_RES, E>(a, pos);
     }
     if (a.rs_out) a.rs_out[sidx] = t[0];   // this step's t(pos), for the next step's bracket
   }
@@ -621,14 +690,44 @@ __device__ __forceinline__ void st4(float* p, int64_t i, int64_t n, float4 v) {
   }
 }
 
-template <bool HAS_RES, bool FAST>
+// the same for a bf16 stream: four elements per lane are ONE 8-B nt access, the lane-to-element
+// mapping is the f32 pass's (lane l of a group's u-th row holds elements i0 .. i0 + 3)
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+template <bool FAST>
+__device__ __forceinline__ float4 ld4(const uint16_t* p, int64_t i, int64_t n) {
+  if constexpr (FAST) {
+    const u32x2 w = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p + i));
+    return make_float4(u2f(w.x << 16), u2f(w.x & 0xFFFF0000u), u2f(w.y << 16), u2f(w.y & 0xFFFF0000u));
+  } else {
+    float4 v;
+    v.x = i < n ? bf16_to_f32(p[i]) : 0.f;
+    v.y = i + 1 < n ? bf16_to_f32(p[i + 1]) : 0.f;
+    v.z = i + 2 < n ? bf16_to_f32(p[i + 2]) : 0.f;
+    v.w = i + 3 < n ? bf16_to_f32(p[i + 3]) : 0.f;
+    return v;
+  }
+}
+template <bool FAST>
+__device__ __forceinline__ void st4(uint16_t* p, int64_t i, int64_t n, float4 v) {
+  if constexpr (FAST) {
+    const u32x2 x = {pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)};
+    __builtin_nontemporal_store(x, reinterpret_cast<u32x2*>(p + i));
+  } else {
+    if (i < n) p[i] = f32_to_bf16(v.x);
+    if (i + 1 < n) p[i + 1] = f32_to_bf16(v.y);
+    if (i + 2 < n) p[i + 2] = f32_to_bf16(v.z);
+    if (i + 3 < n) p[i + 3] = f32_to_bf16(v.w);
+  }
+}
+
+template <bool HAS_RES, bool FAST, typename E = float>
 __device__ __forceinline__ void load_group(const StepArgs& a, int64_t gbase, float4 (&rv)[kGroup],
                                            float4 (&gv)[kGroup]) {
 #pragma unroll
   for (int u = 0; u < kGroup; ++u) {
     const int64_t i0 = gbase + (int64_t)u * (kMainBlock * 4);
     if constexpr (HAS_RES) rv[u] = ld4<FAST>(a.r_in, i0, a.n);
-    gv[u] = ld4<FAST>(a.g, i0, a.n);
+    gv[u] = ld4<FAST>(g_of<E>(a), i0, a.n);
   }
 }
 
@@ -701,12 +800,14 @@ __device__ __forceinline__ void spill_entry(const StepArgs& a, const TopkWs& w, 
   }
 }
 
-template <bool HAS_RES, int MODE, bool FAST, bool SKEL = false, bool SPARSE = false, bool UNIT = false>
+template <bool HAS_RES, int MODE, bool FAST, bool SKEL = false, bool SPARSE = false, bool UNIT = false,
+          typename E = float>
 __device__ __forceinline__ uint32_t classify_group(const StepArgs& a, const TopkWs& w, MainShared& sm, uint32_t lo,
                                                    uint32_t hi, uint32_t sh, uint32_t mid, int64_t gbase,
                                                    const float4 (&rc)[kGroup], const float4 (&gc)[kGroup],
                                                    uint32_t wfill) {
   static_assert(kGroup == 4, "sel16 picks from 4 float4 per lane");
+  static_assert(!kIsBf16<E> || (!SKEL && !SPARSE), "bf16: no stream probe, no recycled output");
   // the exact provisional decision (key > mid) per element, where a dense output depends on it
   constexpr bool kDenseProv = kProv<MODE> && (kWritesR<MODE> || (kWritesOut<MODE> && !SPARSE));
   const int64_t n = a.n;
@@ -740,7 +841,7 @@ __device__ __forceinline__ uint32_t classify_group(const StepArgs& a, const Topk
         // lo <= mid <= hi (bracket_publish), so that set is key > mid
         const uint32_t key = abs_key(tv);
         const bool sel = !SKEL && key > mid;
-        set4(rout, j, sel ? tv - tv : tv);
+        if constexpr (!kRKeepsT<MODE, E>) set4(rout, j, sel ? tv - tv : tv);
         if constexpr (kWritesOut<MODE> && !SPARSE) set4(dout, j, sel ? 0.f + tv : 0.f);
         f = key >= lo;
       } else {
@@ -753,7 +854,7 @@ __device__ __forceinline__ uint32_t classify_group(const StepArgs& a, const Topk
       m = m + m + (f ? 1u : 0u);
     }
     if constexpr (kWritesR<MODE>) st4<FAST>(a.r, i0, n, rout);
-    if constexpr (kWritesOut<MODE> && !SPARSE) st4<FAST>(a.out, i0, n, dout);
+    if constexpr (kWritesOut<MODE> && !SPARSE) st4<FAST>(out_of<E>(a), i0, n, dout);
   }
   if constexpr (SKEL) return wfill;
   const uint32_t cnt = __popc(m);
@@ -870,16 +971,17 @@ __device__ __forceinline__ void flush_staged(const StepArgs& a, const TopkWs& w,
 // classify_group for the rotating-copy loops of main_chunk.  Only an extra level of inlining, but
 // without it hipcc orders two index adds of those loops differently; kept so that the kernels stay
 // instruction for instruction what was measured.
-template <bool HAS_RES, int MODE, bool FAST, bool SKEL = false, bool SPARSE = false, bool UNIT = false>
+template <bool HAS_RES, int MODE, bool FAST, bool SKEL = false, bool SPARSE = false, bool UNIT = false,
+          typename E = float>
 __device__ __forceinline__ uint32_t classify_group_sel(const StepArgs& a, const TopkWs& w, MainShared& sm, uint32_t lo,
                                                        uint32_t hi, uint32_t sh, uint32_t mid, int64_t gbase,
                                                        const float4 (&rc)[kGroup], const float4 (&gc)[kGroup],
                                                        uint32_t wfill) {
-  return classify_group<HAS_RES, MODE, FAST, SKEL, SPARSE, UNIT>(a, w, sm, lo, hi, sh, mid, gbase, rc, gc, wfill);
+  return classify_group<HAS_RES, MODE, FAST, SKEL, SPARSE, UNIT, E>(a, w, sm, lo, hi, sh, mid, gbase, rc, gc, wfill);
 }
 
 template <bool HAS_RES, int MODE, bool FAST, bool SKEL = false, bool SPARSE = false, bool UNIT = false,
-          int NV = kVecOf<HAS_RES, MODE>>
+          int NV = kVecOf<HAS_RES, MODE>, typename E = float>
 __device__ __forceinline__ uint32_t main_chunk(const StepArgs& a, const TopkWs& w, MainShared& sm,
                                                uint32_t lo, uint32_t hi, uint32_t sh, uint32_t mid, int64_t chunk) {
   constexpr int NG = NV / kGroup;
@@ -897,14 +999,14 @@ __device__ __forceinline__ uint32_t main_chunk(const StepArgs& a, const TopkWs& 
     float4 rb[R][kGroup], gb[R][kGroup];
 #pragma unroll
     for (int p = 0; p < R - 1; ++p)
-      if (p < NG) load_group<HAS_RES, FAST>(a, cbase + p * S, rb[p], gb[p]);
+      if (p < NG) load_group<HAS_RES, FAST, E>(a, cbase + p * S, rb[p], gb[p]);
 #pragma unroll
     for (int q = 0; q < NG; ++q) {
       // no instruction crosses a group boundary: the scheduler would otherwise hoist later groups'
       // loads and spill (the unrolled ring at 128 VGPRs with 15-70 spilled)
       __builtin_amdgcn_sched_barrier(0);
-      if (q + R - 1 < NG) load_group<HAS_RES, FAST>(a, cbase + (q + R - 1) * S, rb[(q + R - 1) % R], gb[(q + R - 1) % R]);
-      wfill = classify_group<HAS_RES, MODE, FAST, SKEL, SPARSE, UNIT>(a, w, sm, lo, hi, sh, mid, cbase + q * S,
+      if (q + R - 1 < NG) load_group<HAS_RES, FAST, E>(a, cbase + (q + R - 1) * S, rb[(q + R - 1) % R], gb[(q + R - 1) % R]);
+      wfill = classify_group<HAS_RES, MODE, FAST, SKEL, SPARSE, UNIT, E>(a, w, sm, lo, hi, sh, mid, cbase + q * S,
                                                                       rb[q % R], gb[q % R], wfill);
     }
     return wfill;
@@ -915,25 +1017,25 @@ __device__ __forceinline__ uint32_t main_chunk(const StepArgs& a, const TopkWs& 
     // one input stream (g only): the loads run TWO groups ahead, so a lane keeps as many bytes in
     // flight as with the residual stream (8 x 16 B)
     float4 g1[kGroup], g2[kGroup];
-    load_group<false, FAST>(a, cbase, rc, gc);
-    load_group<false, FAST>(a, cbase + kGroup * (kMainBlock * 4), rc, g1);
+    load_group<false, FAST, E>(a, cbase, rc, gc);
+    load_group<false, FAST, E>(a, cbase + kGroup * (kMainBlock * 4), rc, g1);
 #pragma unroll 1
     for (int q = 0; q < NG; ++q) {
       const int64_t gbase = cbase + (int64_t)q * kGroup * (kMainBlock * 4);
-      if (q + 2 < NG) load_group<false, FAST>(a, gbase + 2 * kGroup * (kMainBlock * 4), rc, g2);
-      wfill = classify_group_sel<false, MODE, FAST, SKEL, SPARSE, UNIT>(a, w, sm, lo, hi, sh, mid, gbase, rc, gc, wfill);
+      if (q + 2 < NG) load_group<false, FAST, E>(a, gbase + 2 * kGroup * (kMainBlock * 4), rc, g2);
+      wfill = classify_group_sel<false, MODE, FAST, SKEL, SPARSE, UNIT, E>(a, w, sm, lo, hi, sh, mid, gbase, rc, gc, wfill);
 #pragma unroll
       for (int u = 0; u < kGroup; ++u) { gc[u] = g1[u]; g1[u] = g2[u]; }
     }
     return wfill;
   }
-  load_group<HAS_RES, FAST>(a, cbase, rc, gc);
+  load_group<HAS_RES, FAST, E>(a, cbase, rc, gc);
 #pragma unroll 1
   for (int q = 0; q < NG; ++q) {
     const int64_t gbase = cbase + (int64_t)q * kGroup * (kMainBlock * 4);
     float4 rn[kGroup], gn[kGroup];
-    if (q + 1 < NG) load_group<HAS_RES, FAST>(a, gbase + kGroup * (kMainBlock * 4), rn, gn);
-    wfill = classify_group_sel<HAS_RES, MODE, FAST, SKEL, SPARSE, UNIT>(a, w, sm, lo, hi, sh, mid, gbase, rc, gc, wfill);
+    if (q + 1 < NG) load_group<HAS_RES, FAST, E>(a, gbase + kGroup * (kMainBlock * 4), rn, gn);
+    wfill = classify_group_sel<HAS_RES, MODE, FAST, SKEL, SPARSE, UNIT, E>(a, w, sm, lo, hi, sh, mid, gbase, rc, gc, wfill);
 #pragma unroll
     for (int u = 0; u < kGroup; ++u) { rc[u] = rn[u]; gc[u] = gn[u]; }
   }
@@ -941,7 +1043,8 @@ __device__ __forceinline__ uint32_t main_chunk(const StepArgs& a, const TopkWs& 
 }
 
 // NV: float4 per lane per chunk
-template <bool HAS_RES, int MODE, bool VEC, bool SKEL = false, bool SPARSE = false, int NV = kVecOf<HAS_RES, MODE>>
+template <bool HAS_RES, int MODE, bool VEC, bool SKEL = false, bool SPARSE = false, int NV = kVecOf<HAS_RES, MODE>,
+          typename E = float>
 __global__ __launch_bounds__(kMainBlock, 4) void topk_main(StepArgs a, TopkWs w) {   // <= 128 VGPRs: 4 WGs/CU
   __shared__ MainShared sm;
   const int tid = threadIdx.x;
@@ -961,11 +1064,11 @@ __global__ __launch_bounds__(kMainBlock, 4) void topk_main(StepArgs a, TopkWs w)
   for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
     uint32_t wfill;
     if (VEC && (chunk + 1) * kCh <= a.n && unit)
-      wfill = main_chunk<HAS_RES, MODE, VEC, SKEL, SPARSE, true, NV>(a, w, sm, lo, hi, sh, mid, chunk);
+      wfill = main_chunk<HAS_RES, MODE, VEC, SKEL, SPARSE, true, NV, E>(a, w, sm, lo, hi, sh, mid, chunk);
     else if (VEC && (chunk + 1) * kCh <= a.n)
-      wfill = main_chunk<HAS_RES, MODE, VEC, SKEL, SPARSE, false, NV>(a, w, sm, lo, hi, sh, mid, chunk);
+      wfill = main_chunk<HAS_RES, MODE, VEC, SKEL, SPARSE, false, NV, E>(a, w, sm, lo, hi, sh, mid, chunk);
     else
-      wfill = main_chunk<HAS_RES, MODE, false, SKEL, SPARSE, false, NV>(a, w, sm, lo, hi, sh, mid, chunk);
+      wfill = main_chunk<HAS_RES, MODE, false, SKEL, SPARSE, false, NV, E>(a, w, sm, lo, hi, sh, mid, chunk);
     if constexpr (!SKEL) flush_staged<SPARSE && kWritesOut<MODE>>(a, w, sm, lo, hi, sh, mid, wfill);
     (void)wfill;
   }
@@ -980,17 +1083,17 @@ __global__ __launch_bounds__(kMainBlock, 4) void topk_main(StepArgs a, TopkWs w)
 // ------------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------------
 // selected element sinks shared by the boundary / fallback / small kernels
-template <int MODE>
+template <int MODE, typename E = float>
 __device__ __forceinline__ void emit(const StepArgs& a, uint32_t pos, int64_t i, float v) {
   a.vals[pos] = v;
   a.idx[pos] = (int32_t)(i + a.idx_base);
   if constexpr (kWritesR<MODE>) a.r[i] = v - v;
-  if constexpr (kWritesOut<MODE>) a.out[i] = 0.f + v;   // (0 + d) of the Python sum
+  if constexpr (kWritesOut<MODE>) st_elem(out_of<E>(a), i, 0.f + v);   // (0 + d) of the Python sum
 }
 
 // Ordered (ascending index) single-workgroup write of every element with composite >= T over a
 // source f(i) of length n: payload from `pos0`, dense outputs rewritten for every element.
-template <int MODE, int BLOCK = kSelBlock, typename F>
+template <int MODE, int BLOCK = kSelBlock, typename E = float, typename F>
 __device__ void block_write_selected(const StepArgs& a, const F& f, int64_t n, uint64_t T,
                                      uint32_t pos0, uint32_t* s_w) {
   uint32_t run = pos0;
@@ -1006,10 +1109,10 @@ __device__ void block_write_selected(const StepArgs& a, const F& f, int64_t n, u
     const uint32_t ex = block_excl_scan<BLOCK>(sel ? 1u : 0u, s_w, &tot);
     if (i < n) {
       if (sel) {
-        emit<MODE>(a, run + ex, i, v);
+        emit<MODE, E>(a, run + ex, i, v);
       } else {
         if constexpr (kWritesR<MODE>) a.r[i] = v;
-        if constexpr (kWritesOut<MODE>) a.out[i] = 0.f;
+        if constexpr (kWritesOut<MODE>) st_elem(out_of<E>(a), i, 0.f);
       }
     }
     run += tot;
@@ -1055,14 +1158,15 @@ __device__ __forceinline__ int2 ld_i2(const int2* p) {
 }
 
 // t as recorded by the main pass (fallback input); agent-scope loads when AG
-template <int MODE, bool AG>
+template <int MODE, bool AG, typename E = float>
 struct MainTs {
-  const float* g; const float* r; const float* out;
+  const E* g; const float* r;
+  const float* out;   // read only by the f32 kDenseFused pass (t parked in the dense output)
   const float* rin; float beta, gamma;   // kResSwap: t recomputed from g and the untouched r_in
   __device__ float operator()(int64_t i) const {
-    if constexpr (MODE == kDenseNone || MODE == kDenseOut) return g[i];
-    if constexpr (MODE == kResSwap) return rin ? beta * rin[i] + gamma * g[i] : g[i];
-    if constexpr (MODE == kDenseRes) return ld_f32<AG>(r + i);
+    if constexpr (MODE == kDenseNone || MODE == kDenseOut) return ld_elem(g, i);
+    if constexpr (MODE == kResSwap) return rin ? beta * rin[i] + gamma * ld_elem(g, i) : ld_elem(g, i);
+    if constexpr (kRKeepsT<MODE, E>) return ld_f32<AG>(r + i);
     const float o = ld_f32<AG>(out + i), rr = ld_f32<AG>(r + i);   // both issued: no dependent load
     return f2u(o) != 0u ? o : rr;
   }
@@ -1071,15 +1175,15 @@ struct MainTs {
     if constexpr (AG) {
       return make_float4((*this)(i), (*this)(i + 1), (*this)(i + 2), (*this)(i + 3));
     } else {
-      if constexpr (MODE == kDenseNone || MODE == kDenseOut) return *reinterpret_cast<const float4*>(g + i);
+      if constexpr (MODE == kDenseNone || MODE == kDenseOut) return ld_quad(g, i);
       if constexpr (MODE == kResSwap) {
-        const float4 gg = *reinterpret_cast<const float4*>(g + i);
+        const float4 gg = ld_quad(g, i);
         if (!rin) return gg;
         const float4 rr = *reinterpret_cast<const float4*>(rin + i);
         return make_float4(beta * rr.x + gamma * gg.x, beta * rr.y + gamma * gg.y, beta * rr.z + gamma * gg.z,
                            beta * rr.w + gamma * gg.w);
       }
-      if constexpr (MODE == kDenseRes) return *reinterpret_cast<const float4*>(r + i);
+      if constexpr (kRKeepsT<MODE, E>) return *reinterpret_cast<const float4*>(r + i);
       const float4 o = *reinterpret_cast<const float4*>(out + i), rr = *reinterpret_cast<const float4*>(r + i);
       return make_float4(f2u(o.x) != 0u ? o.x : rr.x, f2u(o.y) != 0u ? o.y : rr.y, f2u(o.z) != 0u ? o.z : rr.z,
                          f2u(o.w) != 0u ? o.w : rr.w);
@@ -1107,18 +1211,18 @@ __device__ __forceinline__ bool boundary_preload(const TopkWs& w, bool ok, uint3
 }
 
 // boundary-bin entry not selected: in the fused mode undo a provisional selection (key > mid)
-template <int MODE>
+template <int MODE, typename E = float>
 __device__ __forceinline__ void unselect(const StepArgs& a, int2 e, uint32_t mid) {
   if constexpr (kProv<MODE>) {
     const float v = u2f((uint32_t)e.y);
     if (abs_key(v) > mid) {
-      if constexpr (kWritesR<MODE>) a.r[e.x] = v;
-      if constexpr (kWritesOut<MODE>) a.out[e.x] = 0.f;
+      if constexpr (kWritesR<MODE> && !kRKeepsT<MODE, E>) a.r[e.x] = v;
+      if constexpr (kWritesOut<MODE>) st_elem(out_of<E>(a), e.x, 0.f);
     }
   }
 }
 
-template <int MODE, int BLOCK, bool AG>
+template <int MODE, int BLOCK, bool AG, typename E = float>
 __device__ void boundary_work(const StepArgs& a, const TopkWs& w, bool ok, uint32_t need, uint32_t nb,
                               FinShared<BLOCK>& fs, bool preloaded, uint32_t mid) {
   const uint32_t k = (uint32_t)a.k;
@@ -1145,8 +1249,8 @@ __device__ void boundary_work(const StepArgs& a, const TopkWs& w, bool ok, uint3
         if (part == 0) {
           const int2 e = fs.s_ent[el];
           if (rank == need - 1) carry_threshold(a, me);
-          if (rank < need) emit<MODE>(a, pos0 + rank, e.x, u2f((uint32_t)e.y));
-          else unselect<MODE>(a, e, mid);
+          if (rank < need) emit<MODE, E>(a, pos0 + rank, e.x, u2f((uint32_t)e.y));
+          else unselect<MODE, E>(a, e, mid);
         }
       }
       return;
@@ -1163,26 +1267,26 @@ __device__ void boundary_work(const StepArgs& a, const TopkWs& w, bool ok, uint3
       const int2 e = ld_agent_i2(bnd + j);
       if (comp_key(abs_key(u2f((uint32_t)e.y)), (uint32_t)e.x) >= T) {
         const uint32_t p = atomicAdd(&fs.s_pos, 1u);
-        emit<MODE>(a, pos0 + p, e.x, u2f((uint32_t)e.y));
+        emit<MODE, E>(a, pos0 + p, e.x, u2f((uint32_t)e.y));
       } else {
-        unselect<MODE>(a, e, mid);
+        unselect<MODE, E>(a, e, mid);
       }
     }
     return;
   }
   // ---- exact fallback over the whole bucket (bracket failed or a list overflowed)
   if (threadIdx.x == 0) w.ctl->status = 1;
-  const MainTs<MODE, AG> f{a.g, a.r, a.out, a.r_in != a.r ? a.r_in : nullptr, a.beta, a.gamma};
+  const MainTs<MODE, AG, E> f{g_of<E>(a), a.r, a.out, a.r_in != a.r ? a.r_in : nullptr, a.beta, a.gamma};
   auto src = [f](int64_t i) { return comp_key(abs_key(f(i)), (uint32_t)i); };
   const uint64_t T = block_select_comp<BLOCK>(src, a.n, k, fs.hist, fs.s_w, fs.s_res);
   if (threadIdx.x == 0) carry_threshold(a, T);
-  block_write_selected<MODE, BLOCK>(a, f, a.n, T, 0u, fs.s_w);
+  block_write_selected<MODE, BLOCK, E>(a, f, a.n, T, 0u, fs.s_w);
 }
 
 // One round of routed candidates: payload writes of the above-boundary ones (bits of fsel) from
 // slot ps on, and their residual / dense writes -- in the fused mode only where the main pass's
 // provisional decision (key > mid) was wrong, in both directions (fbelow: below the boundary bin).
-template <int MODE>
+template <int MODE, typename E = float>
 __device__ __forceinline__ void write_round(const StepArgs& a, const int2 (&e)[kFinPer], uint32_t fsel,
                                             uint32_t fbelow, uint32_t ps, uint32_t mid, TopkCtl* dbg_ctl = nullptr) {
 #pragma unroll
@@ -1192,17 +1296,17 @@ __device__ __forceinline__ void write_round(const StepArgs& a, const int2 (&e)[k
     if ((fsel >> u) & 1u) {
       a.vals[ps] = v;
       a.idx[ps] = (int32_t)(e[u].x + a.idx_base);
-      if constexpr (MODE == kDenseRes) a.r[e[u].x] = v - v;
+      if constexpr (kRKeepsT<MODE, E>) a.r[e[u].x] = v - v;
       if constexpr (kProv<MODE>) {
         if (!above_mid) {
-          if constexpr (kWritesR<MODE>) a.r[e[u].x] = v - v;
-          if constexpr (kWritesOut<MODE>) a.out[e[u].x] = 0.f + v;
+          if constexpr (kWritesR<MODE> && !kRKeepsT<MODE, E>) a.r[e[u].x] = v - v;
+          if constexpr (kWritesOut<MODE>) st_elem(out_of<E>(a), e[u].x, 0.f + v);
         }
       }
       ++ps;
     } else if (kProv<MODE> && ((fbelow >> u) & 1u) && above_mid) {
-      if constexpr (kWritesR<MODE>) a.r[e[u].x] = v;
-      if constexpr (kWritesOut<MODE>) a.out[e[u].x] = 0.f;
+      if constexpr (kWritesR<MODE> && !kRKeepsT<MODE, E>) a.r[e[u].x] = v;
+      if constexpr (kWritesOut<MODE>) st_elem(out_of<E>(a), e[u].x, 0.f);
     }
   }
 #ifdef GRACE_STAMPS   // diagnostic: fix-up writes of this round (ctl stamp slot 18: selected below mid, 19: rejected above)
@@ -1293,19 +1397,19 @@ __device__ __forceinline__ void hist_add_agg(uint32_t* hist, int bin) {
 constexpr int kFbUnroll = 8;   // parallel fallback: elements per thread per ordered-write round
 constexpr int kFbQ = 8;        // parallel fallback: quads in flight per thread (histogram / count passes)
 
-template <int MODE, int BLOCK, bool AG>
+template <int MODE, int BLOCK, bool AG, typename E = float>
 __device__ void parallel_exact(const StepArgs& a, const TopkWs& w, int fcnt, FinShared<BLOCK>& fs) {
   const int t = threadIdx.x;
   const uint32_t k = (uint32_t)a.k;
   uint32_t* fb = w.fb;
   // slices of whole quads (16-B loads) when the buffers are 16-B aligned; [q1, s1) is a scalar tail
-  const bool vq = !AG && ((reinterpret_cast<uintptr_t>(a.g) | reinterpret_cast<uintptr_t>(a.r) |
-                           reinterpret_cast<uintptr_t>(a.out)) & 15u) == 0;
+  // (8-B accesses of a bf16 gradient / output)
+  const bool vq = !AG && quad_aligned<E>(a);
   int64_t L = (a.n + kFbSlicesMax - 1) / kFbSlicesMax;
   L = L < kFbSliceMin ? kFbSliceMin : ((L + 3) & ~(int64_t)3);
   const uint32_t nsl = (uint32_t)((a.n + L - 1) / L);
   if (t == 0) __hip_atomic_fetch_max(&w.ctl->status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const MainTs<MODE, AG> f{a.g, a.r, a.out, a.r_in != a.r ? a.r_in : nullptr, a.beta, a.gamma};
+  const MainTs<MODE, AG, E> f{g_of<E>(a), a.r, a.out, a.r_in != a.r ? a.r_in : nullptr, a.beta, a.gamma};
   auto bounds = [&](uint32_t s, int64_t& s0, int64_t& q1, int64_t& s1) {
     s0 = (int64_t)s * L;
     s1 = s0 + L < a.n ? s0 + L : a.n;
@@ -1472,15 +1576,15 @@ __device__ void parallel_exact(const StepArgs& a, const TopkWs& w, int fcnt, Fin
               *reinterpret_cast<float4*>(a.r + ib + 4) = make_float4(rv[4], rv[5], rv[6], rv[7]);
             }
             if constexpr (kWritesOut<MODE>) {
-              *reinterpret_cast<float4*>(a.out + ib) = make_float4(ov[0], ov[1], ov[2], ov[3]);
-              *reinterpret_cast<float4*>(a.out + ib + 4) = make_float4(ov[4], ov[5], ov[6], ov[7]);
+              st_quad(out_of<E>(a), ib, make_float4(ov[0], ov[1], ov[2], ov[3]));
+              st_quad(out_of<E>(a), ib + 4, make_float4(ov[4], ov[5], ov[6], ov[7]));
             }
           } else {
 #pragma unroll
             for (int u = 0; u < kFbUnroll; ++u) {
               if (ib + u < s1) {
                 if constexpr (kWritesR<MODE>) a.r[ib + u] = rv[u];
-                if constexpr (kWritesOut<MODE>) a.out[ib + u] = ov[u];
+                if constexpr (kWritesOut<MODE>) st_elem(out_of<E>(a), ib + u, ov[u]);
               }
             }
           }
@@ -1501,7 +1605,7 @@ __device__ void parallel_exact(const StepArgs& a, const TopkWs& w, int fcnt, Fin
 }
 
 // finalize workgroup `fi` of `fcnt`; returns true in the workgroup that ran the boundary step
-template <int MODE, int BLOCK, bool AG>
+template <int MODE, int BLOCK, bool AG, typename E = float>
 __device__ bool finalize_run(const StepArgs& a, const TopkWs& w, int fi, int fcnt, FinShared<BLOCK>& fs,
                              bool parallel) {
   constexpr int PER = kHistBins / BLOCK;
@@ -1529,7 +1633,7 @@ __device__ bool finalize_run(const StepArgs& a, const TopkWs& w, int fi, int fcn
   // a caller without its scratch (segmented: per-tensor workspaces) lets the last workgroup alone
   // run the single-workgroup exact select below (same result, slower)
   if (!ok && parallel && fcnt > 1) {
-    parallel_exact<MODE, BLOCK, AG>(a, w, fcnt, fs);
+    parallel_exact<MODE, BLOCK, AG, E>(a, w, fcnt, fs);
     return fi == 0;
   }
   int B = -1;
@@ -1569,7 +1673,7 @@ __device__ bool finalize_run(const StepArgs& a, const TopkWs& w, int fi, int fcn
     // residual-only mode: sure entries still hold t in r; zero them now
     // (kFinPer entries per thread per round, every load issued before any store: one dependent
     // load -> store chain per entry made this 14 us of the finalize at k = 671 K)
-    if constexpr (MODE == kDenseRes) {
+    if constexpr (kRKeepsT<MODE, E>) {
       const uint32_t stride = (uint32_t)(fcnt * BLOCK);
       for (uint32_t j0 = fi * BLOCK + t; j0 < n_sure; j0 += stride * kFinPer) {
         float v[kFinPer];
@@ -1622,7 +1726,7 @@ __device__ bool finalize_run(const StepArgs& a, const TopkWs& w, int fi, int fcn
 #pragma unroll
         for (int u = 0; u < kFinPer; ++u)
           if ((fb >> u) & 1u) st_agent_i2(w.bnd + pb++, e[u]);
-        if (!defer) write_round<MODE>(a, e, fsel, fbelow, ps, mid, w.ctl);
+        if (!defer) write_round<MODE, E>(a, e, fsel, fbelow, ps, mid, w.ctl);
       }
     }
   }
@@ -1635,28 +1739,28 @@ __device__ bool finalize_run(const StepArgs& a, const TopkWs& w, int fi, int fcn
   __syncthreads();
   const bool last = fs.s_last;
   const bool preloaded = last && boundary_preload<BLOCK>(w, ok, need, nb, fs);
-  if (defer) write_round<MODE>(a, e, fsel, fbelow, ps, mid, w.ctl);
+  if (defer) write_round<MODE, E>(a, e, fsel, fbelow, ps, mid, w.ctl);
   if (!last) return false;
   STAMP_IF(true, w.ctl, 11);
-  boundary_work<MODE, BLOCK, AG>(a, w, ok, need, nb, fs, preloaded, mid);
+  boundary_work<MODE, BLOCK, AG, E>(a, w, ok, need, nb, fs, preloaded, mid);
   __syncthreads();
   STAMP_IF(true, w.ctl, 12);
   return true;
 }
 
-template <int MODE>
+template <int MODE, typename E = float>
 __global__ __launch_bounds__(kSelBlock) void topk_finalize(StepArgs a, TopkWs w) {
   __shared__ FinShared<kSelBlock> fs;
   STAMP(w.ctl, 8);
-  finalize_run<MODE, kSelBlock, false>(a, w, blockIdx.x, gridDim.x, fs, true);
+  finalize_run<MODE, kSelBlock, false, E>(a, w, blockIdx.x, gridDim.x, fs, true);
 }
 
 // ------------------------------------------------------------------------------------------------
 // small buckets: everything in one workgroup, t staged in LDS
-template <bool HAS_RES, int MODE>
+template <bool HAS_RES, int MODE, typename E = float>
 __device__ void small_body(const StepArgs& a, float* s_t, uint32_t* hist, uint32_t* s_w, uint32_t* s_res) {
   const int64_t n = a.n;
-  for (int64_t i = threadIdx.x; i < n; i += kSelBlock) s_t[i] = compensate<HAS_RES>(a, i);
+  for (int64_t i = threadIdx.x; i < n; i += kSelBlock) s_t[i] = compensate<HAS_RES, E>(a, i);
   __syncthreads();
   const float* st = s_t;
   auto src = [st](int64_t i) { return comp_key(abs_key(st[i]), (uint32_t)i); };
@@ -1664,59 +1768,59 @@ __device__ void small_body(const StepArgs& a, float* s_t, uint32_t* hist, uint32
   uint64_t T = 0;
   if ((int64_t)k < n) T = block_select_comp(src, n, k, hist, s_w, s_res);
   auto f = [st](int64_t i) { return st[i]; };
-  block_write_selected<MODE>(a, f, n, T, 0u, s_w);
+  block_write_selected<MODE, kSelBlock, E>(a, f, n, T, 0u, s_w);
 }
 
-template <bool HAS_RES, int MODE>
+template <bool HAS_RES, int MODE, typename E = float>
 __global__ __launch_bounds__(kSelBlock) void topk_small(StepArgs a) {
   __shared__ float s_t[kSmallN];
   __shared__ uint32_t hist[2048];
   __shared__ uint32_t s_w[kSelBlock / kWave + 1];
   __shared__ uint32_t s_res[2];
-  small_body<HAS_RES, MODE>(a, s_t, hist, s_w, s_res);
+  small_body<HAS_RES, MODE, E>(a, s_t, hist, s_w, s_res);
 }
 
 // ------------------------------------------------------------------------------------------------
 // k >= n on a large bucket: every element is selected, payload in index order
-template <bool HAS_RES, int MODE>
+template <bool HAS_RES, int MODE, typename E = float>
 __global__ __launch_bounds__(256) void topk_all(StepArgs a) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n;
        i += (int64_t)gridDim.x * blockDim.x)
-    emit<MODE>(a, (uint32_t)i, i, compensate<HAS_RES>(a, i));
+    emit<MODE, E>(a, (uint32_t)i, i, compensate<HAS_RES, E>(a, i));
 }
 
 constexpr int kNoresBigVec = 64;
 constexpr int64_t kNoresBigMinN = (int64_t)1024 * kMainBlock * 4 * kNoresBigVec;   // 2^26 at 64
 
 // the main pass at NV float4 per lane per chunk (one chunk per workgroup)
-template <bool HAS_RES, int MODE, int NV>
+template <bool HAS_RES, int MODE, int NV, typename E = float>
 static void launch_main(const StepArgs& a, const TopkWs& w, bool sparse, bool vec, hipStream_t s) {
   constexpr int64_t kCh = (int64_t)kMainBlock * 4 * NV;
   const unsigned nblk = (unsigned)((a.n + kCh - 1) / kCh);
   if (sparse) {
-    if constexpr (kWritesOut<MODE>) {
+    if constexpr (kWritesOut<MODE> && !kIsBf16<E>) {
       if (vec)
         launch_timed(topk_main<HAS_RES, MODE, true, false, true, NV>, dim3(nblk), dim3(kMainBlock), s, a, w);
       else
         launch_timed(topk_main<HAS_RES, MODE, false, false, true, NV>, dim3(nblk), dim3(kMainBlock), s, a, w);
     }
   } else if (vec) {
-    launch_timed(topk_main<HAS_RES, MODE, true, false, false, NV>, dim3(nblk), dim3(kMainBlock), s, a, w);
+    launch_timed(topk_main<HAS_RES, MODE, true, false, false, NV, E>, dim3(nblk), dim3(kMainBlock), s, a, w);
   } else {
-    launch_timed(topk_main<HAS_RES, MODE, false, false, false, NV>, dim3(nblk), dim3(kMainBlock), s, a, w);
+    launch_timed(topk_main<HAS_RES, MODE, false, false, false, NV, E>, dim3(nblk), dim3(kMainBlock), s, a, w);
   }
 }
 
-template <bool HAS_RES, int MODE>
+template <bool HAS_RES, int MODE, typename E = float>
 static grace_status_t run_topk(StepArgs a, void* ws, size_t bytes, hipStream_t s) {
   if (!a.r_in) a.r_in = a.r;
   if (a.n <= kSmallN) {
-    topk_small<HAS_RES, MODE><<<1, kSelBlock, 0, s>>>(a);
+    topk_small<HAS_RES, MODE, E><<<1, kSelBlock, 0, s>>>(a);
     GRACE_CHECK_LAUNCH("topk_small");
     return GRACE_OK;
   }
   if (a.k >= a.n) {
-    topk_all<HAS_RES, MODE><<<stream_grid(a.n, 256), 256, 0, s>>>(a);
+    topk_all<HAS_RES, MODE, E><<<stream_grid(a.n, 256), 256, 0, s>>>(a);
     GRACE_CHECK_LAUNCH("topk_all");
     return GRACE_OK;
   }
@@ -1725,21 +1829,21 @@ static grace_status_t run_topk(StepArgs a, void* ws, size_t bytes, hipStream_t s
     return GRACE_ERR_WORKSPACE;
   }
   TopkWs w = carve(ws, a.n, a.k);
-  const bool vec = ((reinterpret_cast<uintptr_t>(a.g) | reinterpret_cast<uintptr_t>(a.r) |
-                     reinterpret_cast<uintptr_t>(a.out)) & 15u) == 0;
+  const bool vec = quad_aligned<E>(a);   // else the guarded path (as the bucket's tail of n mod 4 elements)
   a.sample_n = bracket_sample_n(a.n);
   a.stratum = a.n / a.sample_n;
   if (a.stratum < kCarryMinStratum) a.rs_in = a.rs_out = nullptr;   // (grace_topk_carry_size says 0)
   // >= 33 sample workgroups (n > kSmallN): the first two zero the candidate histogram
   static_assert(kSmallN >= kHistBins, "bracket grid covers the histogram zeroing");
-  const bool sparse = kWritesOut<MODE> && a.out && a.prev_idx && a.prev_count > 0;
+  // (bf16: never recycled -- its entry points take no prev_idx)
+  const bool sparse = !kIsBf16<E> && kWritesOut<MODE> && a.out && a.prev_idx && a.prev_count > 0;
   if (!sparse) a.prev_idx = nullptr;
   const unsigned nclr = sparse ? (unsigned)min((int64_t)kClearMax, (a.prev_count + kClearPer - 1) / kClearPer) : 0u;
-  topk_bracket<HAS_RES><<<(unsigned)((a.sample_n + kBracketBlock - 1) / kBracketBlock) + nclr,
+  topk_bracket<HAS_RES, E><<<(unsigned)((a.sample_n + kBracketBlock - 1) / kBracketBlock) + nclr,
                           kBracketBlock, 0, s>>>(a, w);
   GRACE_CHECK_LAUNCH("topk_bracket");
   bool big = false;
-  if constexpr (!HAS_RES && kVecOf<HAS_RES, MODE> == kMainVecNoRes) {
+  if constexpr (!HAS_RES && !kIsBf16<E> && kVecOf<HAS_RES, MODE> == kMainVecNoRes) {
     // 4 / 8 B per element (no residual stream): large buckets take chunks of kNoresBigVec float4 per
     // lane, so that the grid is ONE balanced generation (2^26 elements: 1024 workgroups, 4 per CU;
     // 32 float4 gave 2048 for 1536 resident slots).  r06 A/B (256 MiB, 1 %): main
@@ -1750,7 +1854,7 @@ static grace_status_t run_topk(StepArgs a, void* ws, size_t bytes, hipStream_t s
     big = a.n >= kNoresBigMinN && a.k <= a.n / 50;
     if (big) launch_main<HAS_RES, MODE, kNoresBigVec>(a, w, sparse, vec, s);
   }
-  if (!big) launch_main<HAS_RES, MODE, kVecOf<HAS_RES, MODE>>(a, w, sparse, vec, s);
+  if (!big) launch_main<HAS_RES, MODE, kVecOf<HAS_RES, MODE, E>, E>(a, w, sparse, vec, s);
   GRACE_CHECK_LAUNCH("topk_main");
   // finalize workgroups by the candidate capacity -- one routing round (kSelBlock * kFinPer
   // candidates) each for the band the bracket can produce -- and by the bucket (at most 2^19
@@ -1762,7 +1866,7 @@ static grace_status_t run_topk(StepArgs a, void* ws, size_t bytes, hipStream_t s
     const int64_t c = std::max(w.cap / ((int64_t)kSelBlock * kFinPer) + 1, a.n >> 19);
     fblocks = (int)(c < 16 ? 16 : (c > kFinBlocks ? kFinBlocks : c));
   }
-  topk_finalize<MODE><<<fblocks, kSelBlock, 0, s>>>(a, w);
+  topk_finalize<MODE, E><<<fblocks, kSelBlock, 0, s>>>(a, w);
   GRACE_CHECK_LAUNCH("topk_finalize");
   return GRACE_OK;
 }
@@ -2350,6 +2454,76 @@ grace_status_t grace_topk_residual_step_swap(const float* g, const float* r_in, 
   if (has_residual) return run_topk<true, kResSwap>(a, ws, ws_bytes_, s);
   a.r_in = a.r;   // (never read without a residual; distinct from nothing)
   return run_topk<false, kResSwap>(a, ws, ws_bytes_, s);
+}
+
+// ---- bfloat16 gradients (and dense results), f32 residual and payload: every result is what the
+// f32 entry point above computes for the gradient widened to f32, the dense result rounded to
+// bf16 (nearest even).  StepArgs carries the bf16 buffers in its float-typed g / out fields (g_of /
+// out_of); no recycled output, so no prev_idx.
+static inline const float* as_g(const uint16_t* p) { return reinterpret_cast<const float*>(p); }
+static inline float* as_out(uint16_t* p) { return reinterpret_cast<float*>(p); }
+
+grace_status_t grace_topk_compress_bf16(const uint16_t* x, int64_t n, int64_t k, float* vals, int32_t* idx,
+                                        void* ws, size_t ws_bytes_, void* stream) {
+  GRACE_REQUIRE(x && vals && idx && n > 0 && k >= 1 && k <= n && n < (int64_t)1 << 31,
+                "grace_topk_compress_bf16: bad arguments");
+  GRACE_REQUIRE(n <= kSmallN || ws, "grace_topk_compress_bf16: workspace required");
+  StepArgs a{as_g(x), nullptr, 1.f, 1.f, n, k, vals, idx, nullptr};
+  return run_topk<false, kDenseNone, uint16_t>(a, ws, ws_bytes_, as_stream(stream));
+}
+
+grace_status_t grace_topk_step_dense_bf16(const uint16_t* x, int64_t n, int64_t k, float* vals, int32_t* idx,
+                                          uint16_t* out, void* ws, size_t ws_bytes_, void* stream) {
+  GRACE_REQUIRE(x && vals && idx && out && n > 0 && k >= 1 && k <= n && n < (int64_t)1 << 31,
+                "grace_topk_step_dense_bf16: bad arguments");
+  GRACE_REQUIRE(n <= kSmallN || ws, "grace_topk_step_dense_bf16: workspace required");
+  StepArgs a{as_g(x), nullptr, 1.f, 1.f, n, k, vals, idx, as_out(out)};
+  return run_topk<false, kDenseOut, uint16_t>(a, ws, ws_bytes_, as_stream(stream));
+}
+
+grace_status_t grace_topk_residual_step_bf16(const uint16_t* g, float* residual, int32_t has_residual, float beta,
+                                             float gamma, int64_t n, int64_t k, float* vals, int32_t* idx,
+                                             uint16_t* out, float* carry, int64_t carry_len, int32_t carry_valid,
+                                             void* ws, size_t ws_bytes_, void* stream) {
+  GRACE_REQUIRE(g && residual && vals && idx && n > 0 && k >= 1 && k <= n && n < (int64_t)1 << 31,
+                "grace_topk_residual_step_bf16: bad arguments");
+  GRACE_REQUIRE(!carry || carry_len >= grace_topk_carry_size(n, k),
+                "grace_topk_residual_step_bf16: carry shorter than grace_topk_carry_size(n, k)");
+  GRACE_REQUIRE(n <= kSmallN || ws, "grace_topk_residual_step_bf16: workspace required");
+  StepArgs a{as_g(g), residual, beta, gamma, n, k, vals, idx, as_out(out)};
+  if (carry && grace_topk_carry_size(n, k) > 0) {
+    a.rs_out = carry;
+    a.rs_in = has_residual && carry_valid ? carry : nullptr;
+  }
+  hipStream_t s = as_stream(stream);
+  if (out) {
+    return has_residual ? run_topk<true, kDenseFused, uint16_t>(a, ws, ws_bytes_, s)
+                        : run_topk<false, kDenseFused, uint16_t>(a, ws, ws_bytes_, s);
+  }
+  return has_residual ? run_topk<true, kDenseRes, uint16_t>(a, ws, ws_bytes_, s)
+                      : run_topk<false, kDenseRes, uint16_t>(a, ws, ws_bytes_, s);
+}
+
+grace_status_t grace_topk_residual_step_swap_bf16(const uint16_t* g, const float* r_in, int32_t has_residual,
+                                                  float beta, float gamma, int64_t n, int64_t k, float* vals,
+                                                  int32_t* idx, float* r_out, float* carry, int64_t carry_len,
+                                                  int32_t carry_valid, void* ws, size_t ws_bytes_, void* stream) {
+  GRACE_REQUIRE(g && r_out && (!has_residual || r_in) && r_in != r_out && vals && idx && n > 0 && k >= 1 &&
+                    k <= n && n < (int64_t)1 << 31,
+                "grace_topk_residual_step_swap_bf16: bad arguments (r_in and r_out distinct)");
+  GRACE_REQUIRE(!carry || carry_len >= grace_topk_carry_size(n, k),
+                "grace_topk_residual_step_swap_bf16: carry shorter than grace_topk_carry_size(n, k)");
+  GRACE_REQUIRE(n <= kSmallN || ws, "grace_topk_residual_step_swap_bf16: workspace required");
+  StepArgs a{as_g(g), r_out, beta, gamma, n, k, vals, idx, nullptr};
+  a.r_in = has_residual ? r_in : nullptr;
+  if (carry && grace_topk_carry_size(n, k) > 0) {
+    a.rs_out = carry;
+    a.rs_in = has_residual && carry_valid ? carry : nullptr;
+  }
+  hipStream_t s = as_stream(stream);
+  if (has_residual) return run_topk<true, kResSwap, uint16_t>(a, ws, ws_bytes_, s);
+  a.r_in = a.r;
+  return run_topk<false, kResSwap, uint16_t>(a, ws, ws_bytes_, s);
 }
 
 grace_status_t grace_sparse_decode(const float* vals, const int32_t* idx, int64_t count, float* out,

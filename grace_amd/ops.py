@@ -13,6 +13,7 @@ import torch
 from . import _lib
 
 F32 = torch.float32
+BF16 = torch.bfloat16
 
 
 class GraceDeviceError(TypeError):
@@ -52,6 +53,33 @@ def dev_f32(t, what="tensor"):
     if t.dtype != F32:
         raise TypeError(f"grace_amd: {what} must be float32, got {t.dtype}")
     return t.reshape(-1) if t.is_contiguous() else t.contiguous().reshape(-1)
+
+
+def dev_grad(t, what="gradient"):
+    """Flat, contiguous device view of a gradient the top-k engine takes: float32 or bfloat16
+    (bf16 in, bf16 dense result; the residual and the payload stay f32)."""
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise GraceDeviceError(
+            f"grace_amd: {what} must be a GPU tensor (MI355X); got "
+            f"{getattr(t, 'device', type(t))}. There is no CPU path.")
+    if t.dtype != F32 and t.dtype != BF16:
+        raise TypeError(f"grace_amd: {what} must be float32 or bfloat16, got {t.dtype}")
+    return t.reshape(-1) if t.is_contiguous() else t.contiguous().reshape(-1)
+
+
+def _f32_residual(r, n, device):
+    """Whether r can be the residual of a bf16 step: a contiguous f32 tensor of n elements there."""
+    return (isinstance(r, torch.Tensor) and r.dtype == F32 and r.numel() == n and r.is_contiguous()
+            and r.device == device)
+
+
+def _bf16_out(out, n, device, what):
+    """The dense result of a bf16 step: the caller's contiguous bf16 buffer, or a new one."""
+    if out is None:
+        return torch.empty(n, dtype=BF16, device=device)
+    if out.dtype != BF16 or out.numel() != n or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"grace_amd: {what}: out must be a contiguous bfloat16 tensor of {n} elements on {device}")
+    return out
 
 
 def require_dev(t, what="tensor"):
@@ -481,21 +509,32 @@ def new_payload(k, device):
 
 
 def topk_compress(x, k):
-    x = dev_f32(x)
+    """x: float32 or bfloat16; the payload is f32 values and int32 indices either way."""
+    x = dev_grad(x, "tensor")
     n = x.numel()
     buf, vals, idx = new_payload(k, x.device)
     ws = topk_workspace(n, k, x.device)
-    _lib.call("grace_topk_compress", _p(x), n, k, _p(vals), _p(idx), _p(ws), ws.numel(), _stream())
+    _lib.call("grace_topk_compress_bf16" if x.dtype == BF16 else "grace_topk_compress", _p(x), n, k, _p(vals),
+              _p(idx), _p(ws), ws.numel(), _stream())
     return buf, vals, idx
 
 
 def topk_step_dense(x, k, out=None, prev_idx=None):
     """World-1 Allgather(TopK, NoneMemory).step in one streaming pass (grace_topk_step_dense): the
     payload of topk_compress plus the dense (0 + decode) / 1 result; x is only read.  prev_idx: the
-    payload indices of the earlier step whose result `out` still holds unmodified (recycled)."""
-    x = dev_f32(x)
+    payload indices of the earlier step whose result `out` still holds unmodified (recycled).
+    A bfloat16 x gives a bfloat16 result (grace_topk_step_dense_bf16) and is never recycled."""
+    x = dev_grad(x, "tensor")
     n = x.numel()
     buf, vals, idx = new_payload(k, x.device)
+    if x.dtype == BF16:
+        if prev_idx is not None:
+            raise ValueError("grace_amd: a bfloat16 top-k step has no recycled output (prev_idx)")
+        out = _bf16_out(out, n, x.device, "topk_step_dense")
+        ws = topk_workspace(n, k, x.device)
+        _lib.call("grace_topk_step_dense_bf16", _p(x), n, k, _p(vals), _p(idx), _p(out), _p(ws), ws.numel(),
+                  _stream())
+        return buf, vals, idx, out
     out = torch.empty(n, dtype=F32, device=x.device) if out is None else out
     ws = topk_workspace(n, k, x.device)
     _lib.call("grace_topk_step_dense", _p(x), n, k, _p(vals), _p(idx), _p(out), _p(prev_idx),
@@ -508,13 +547,27 @@ def topk_residual_step(g, residual, has_residual, beta, gamma, k, out=None, payl
     """carry: f32[topk_carry_size(n, k)] kept with `residual` (grace_topk_residual_step_carry);
     carry_valid: it holds the samples the previous step of this residual wrote.  prev_idx: int32
     payload indices of the earlier step whose result `out` still holds unmodified (a recycled
-    output: the step zeroes those and writes only its own selection)."""
-    g = dev_f32(g)
+    output: the step zeroes those and writes only its own selection).  A bfloat16 g
+    (grace_topk_residual_step_bf16): `residual` stays f32, `out` (when given) is bfloat16, and
+    there is no recycled output."""
+    g = dev_grad(g)
     n = g.numel()
     buf, vals, idx = new_payload(k, g.device) if payload is None else payload
     ws = topk_workspace(n, k, g.device)
     if carry is not None and (carry.dtype != F32 or not carry.is_contiguous()):
         raise ValueError("grace_amd: the top-k carry is a contiguous float32 device tensor")
+    if g.dtype == BF16:
+        if prev_idx is not None:
+            raise ValueError("grace_amd: a bfloat16 top-k step has no recycled output (prev_idx)")
+        if not _f32_residual(residual, n, g.device):
+            raise ValueError("grace_amd: the residual of a bfloat16 step is a contiguous float32 tensor of its "
+                             "size on its device")
+        if out is not None:
+            _bf16_out(out, n, g.device, "topk_residual_step")
+        _lib.call("grace_topk_residual_step_bf16", _p(g), _p(residual), 1 if has_residual else 0, float(beta),
+                  float(gamma), n, k, _p(vals), _p(idx), _p(out), _p(carry), carry.numel() if carry is not None else 0,
+                  1 if carry_valid else 0, _p(ws), ws.numel(), _stream())
+        return buf, vals, idx
     if prev_idx is not None and (out is None or prev_idx.dtype != torch.int32 or not prev_idx.is_contiguous()):
         raise ValueError("grace_amd: prev_idx needs an output and contiguous int32 indices")
     if carry is None and prev_idx is None:
@@ -531,14 +584,20 @@ def topk_residual_step(g, residual, has_residual, beta, gamma, k, out=None, payl
 def topk_residual_step_swap(g, residual, has_residual, beta, gamma, k, residual_out, payload=None, carry=None,
                             carry_valid=False):
     """The world > 1 residual step into a second residual buffer (grace_topk_residual_step_swap):
-    reads g and `residual`, writes `residual_out` (distinct) and the payload."""
-    g = dev_f32(g)
+    reads g and `residual`, writes `residual_out` (distinct) and the payload.  g: float32 or
+    bfloat16 (grace_topk_residual_step_swap_bf16); both residual buffers are f32."""
+    g = dev_grad(g)
     n = g.numel()
     buf, vals, idx = new_payload(k, g.device) if payload is None else payload
     ws = topk_workspace(n, k, g.device)
     if residual_out is None or residual_out.data_ptr() == (residual.data_ptr() if residual is not None else 0):
         raise ValueError("grace_amd: topk_residual_step_swap needs a distinct residual_out")
-    _lib.call("grace_topk_residual_step_swap", _p(g), _p(residual) if has_residual else None, 1 if has_residual else 0,
+    if g.dtype == BF16 and not (_f32_residual(residual_out, n, g.device)
+                                and (not has_residual or _f32_residual(residual, n, g.device))):
+        raise ValueError("grace_amd: the residuals of a bfloat16 step are contiguous float32 tensors of its size "
+                         "on its device")
+    _lib.call("grace_topk_residual_step_swap_bf16" if g.dtype == BF16 else "grace_topk_residual_step_swap",
+              _p(g), _p(residual) if has_residual else None, 1 if has_residual else 0,
               float(beta), float(gamma), n, k, _p(vals), _p(idx), _p(residual_out), _p(carry),
               carry.numel() if carry is not None else 0, 1 if carry_valid else 0, _p(ws), ws.numel(), _stream())
     return buf, vals, idx
@@ -884,6 +943,17 @@ def fp16_compress(x, out=None):
     h = _out_buf(out, x.numel(), torch.float16, x.device, "fp16_compress")
     _lib.call("grace_fp16_compress", _p(x), _p(h), x.numel(), _stream())
     return h
+
+
+def f32_to_bf16(x, out=None):
+    """x rounded to bfloat16 (nearest even, as torch's CPU cast) by grace_f32_to_bf16; same shape."""
+    flat = dev_f32(x)
+    if out is None:
+        out = torch.empty(x.shape, dtype=BF16, device=flat.device)
+    else:
+        _bf16_out(out, flat.numel(), flat.device, "f32_to_bf16")
+    _lib.call("grace_f32_to_bf16", _p(flat), _p(out), flat.numel(), _stream())
+    return out
 
 
 def fp16_decompress(h):

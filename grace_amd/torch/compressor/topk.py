@@ -14,7 +14,7 @@ class TopKCompressor(Compressor):
         self.compress_ratio = compress_ratio
 
     def compress(self, tensor, name):
-        flat = ops.dev_f32(tensor)
+        flat = ops.dev_grad(tensor, "tensor")   # float32 or bfloat16; the payload is f32 either way
         k = ops.ratio_k(flat.numel(), self.compress_ratio)
         _, vals, idx32 = ops.topk_compress(flat, k)
         return [vals, ops.widen_i32(idx32)], (tensor.numel(), tensor.size())

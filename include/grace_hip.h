@@ -166,6 +166,28 @@ grace_status_t grace_topk_residual_step_swap(const float* g, const float* r_in, 
 /* TopKCompressor.compress on its own: x is only read. */
 grace_status_t grace_topk_compress(const float* x, int64_t n, int64_t k, float* vals, int32_t* idx,
                                    void* ws, size_t ws_bytes, void* stream);
+/* bfloat16 gradients (g / x) and dense results (out), carried as their 16 bits; the residual, the
+ * payload (vals f32[k], idx int32[k]), the carry and the workspace are the f32 entry points' own
+ * (grace_topk_workspace_bytes, grace_topk_carry_size).  Every result is what the f32 twin computes
+ * for the gradient widened to f32 (exact); the dense result is that twin's rounded to bf16, nearest
+ * even, subnormals included, NaN to a NaN.  No recycled output (no prev_idx).  Vector path: g and
+ * out 8-B aligned, the residual 16-B; anything else takes the guarded path.
+ * grace_topk_residual_step_bf16 is grace_topk_residual_step_carry's twin: out may be NULL (in-place
+ * residual, no dense result: world > 1). */
+grace_status_t grace_topk_compress_bf16(const uint16_t* x, int64_t n, int64_t k, float* vals, int32_t* idx,
+                                        void* ws, size_t ws_bytes, void* stream);
+grace_status_t grace_topk_step_dense_bf16(const uint16_t* x, int64_t n, int64_t k, float* vals, int32_t* idx,
+                                          uint16_t* out, void* ws, size_t ws_bytes, void* stream);
+grace_status_t grace_topk_residual_step_bf16(const uint16_t* g, float* residual, int32_t has_residual, float beta,
+                                             float gamma, int64_t n, int64_t k, float* vals, int32_t* idx,
+                                             uint16_t* out, float* carry, int64_t carry_len, int32_t carry_valid,
+                                             void* ws, size_t ws_bytes, void* stream);
+grace_status_t grace_topk_residual_step_swap_bf16(const uint16_t* g, const float* r_in, int32_t has_residual,
+                                                  float beta, float gamma, int64_t n, int64_t k, float* vals,
+                                                  int32_t* idx, float* r_out, float* carry, int64_t carry_len,
+                                                  int32_t carry_valid, void* ws, size_t ws_bytes, void* stream);
+/* out = bf16(x), round to nearest even as above (the world > 1 decode narrows its f32 result) */
+grace_status_t grace_f32_to_bf16(const float* x, uint16_t* out, int64_t n, void* stream);
 /* Fused world-1 Communicator.step for TopK + NoneMemory (grace_dl/dist/__init__.py:47-51,
  * memory/none.py, allgather.py:40-45): the payload of grace_topk_compress and, in the same
  * streaming pass, out = (0 + zeros(n).scatter_(idx, vals)) / 1.  x is only read.  prev_idx

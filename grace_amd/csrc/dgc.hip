@@ -804,12 +804,17 @@ __global__ void sumsq_finish_kernel(const double* __restrict__ part, int nb, flo
   }
 }
 
-// clamp(x, -c, c) with c = sqrt(s / world) read from the device (after the caller's all_reduce)
+// clamp(x, -c, c) with c = sqrt(s / world) read from the device (after the caller's all_reduce).
+// torch.clamp propagates NaN both ways -- a NaN element stays NaN, a NaN bound (a NaN anywhere in the
+// gradient, through s) makes every element NaN -- and leaves the sign of a zero alone; fminf / fmaxf
+// return the other operand for a NaN, so the clamp is spelt out in compares, which a NaN fails.
 __global__ __launch_bounds__(kDBlock) void clip_kernel(const float* __restrict__ x, const float* __restrict__ s,
                                                       float world, float* __restrict__ out, int64_t n) {
   const float c = sqrtf(*s / world);
-  for (int64_t i = (int64_t)blockIdx.x * kDBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kDBlock)
-    out[i] = fminf(fmaxf(x[i], -c), c);
+  for (int64_t i = (int64_t)blockIdx.x * kDBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kDBlock) {
+    const float v = x[i];
+    out[i] = c != c ? c : (v < -c ? -c : (v > c ? c : v));
+  }
 }
 
 }  // namespace grace

@@ -1436,6 +1436,9 @@ def sumsq(x):
 
 
 def clip_by_sumsq(x, s, world):
+    """DgcMemory's gradient clipping: ``x.clamp(-c, c)`` with ``c = sqrt(s / world)``, s the (all-reduced)
+    sum of squares on the device.  torch.clamp's NaN rule: a NaN element stays NaN, and a NaN s -- a NaN
+    anywhere in any rank's gradient -- makes every element NaN, so a diverged step is never made finite."""
     x = dev_f32(x)
     out = torch.empty_like(x)
     _lib.call("grace_clip_by_sumsq", _p(x), _p(s), float(world), _p(out), x.numel(), _stream())

@@ -472,6 +472,17 @@ def dgc_memory_compensate(g, residual, accum, momentum):
     return a.copy(), r, a
 
 
+def dgc_clip(g, sumsq, world):
+    """DgcMemory.compensate's gradient clipping as documented (memory/dgc.py:18-20), given the
+    all-reduced sum of squares (the reference itself raises there: ``dist.all_reduce`` returns
+    None): ``g.clamp(-c, c)`` with ``c = torch.sqrt(sumsq / world)`` in f32.  torch.clamp
+    propagates NaN from an element and from the bound, and keeps the sign of a zero."""
+    t = torch.from_numpy(_f32(g).ravel().copy())
+    s = torch.tensor(float(np.asarray(sumsq, dtype=F32).reshape(())), dtype=torch.float32)
+    c = torch.sqrt(s / world)
+    return t.clamp(-c, c).numpy()
+
+
 def dgc_memory_update(residual, accum, mask):
     """DgcMemory.update (memory/dgc.py:31-39): r * ~mask, a * ~mask (f32 multiply by 0/1)."""
     keep = (~np.asarray(mask, dtype=bool)).astype(F32)

@@ -157,11 +157,13 @@ def residual_update(t, decoded):
     return (_f32(t).ravel() - _f32(decoded).ravel()).astype(F32)
 
 
-def topk_residual_step(g, residual, ratio, world_size=1):
-    """One Allgather(TopK, ResidualMemory, 1).step on a flat bucket (world 1).
+def topk_residual_step(g, residual, ratio, world_size=1, beta=1.0, gamma=1.0, k=None):
+    """One Allgather(TopK, ResidualMemory(beta, gamma), 1).step on a flat bucket (world 1).
+    ``k`` (optional) sets the payload size directly instead of through ``ratio``.
     Returns (t, vals, idx, new_residual, out)."""
-    t = residual_compensate(g, residual).ravel()
-    k = ratio_k(t.size, ratio)
+    t = residual_compensate(g, residual, beta, gamma).ravel()
+    if k is None:
+        k = ratio_k(t.size, ratio)
     vals, idx = topk_select(t, k)
     dec = sparse_decode(vals, idx, t.size)
     new_res = residual_update(t, dec)

@@ -1786,7 +1786,7 @@ grace_status_t grace_normal_orthogonal(float* A, int64_t n, int32_t r, uint64_t 
 
 grace_status_t grace_powersgd_outer(const float* P, const float* Q, int64_t n, int64_t m, int32_t r, float* out,
                                     const float* M, float* residual, void* stream) {
-  GRACE_REQUIRE(P && Q && n >= 1 && m >= 1 && r >= 1 && (out || (M && residual)) && (!residual || M),
+  GRACE_REQUIRE(P && Q && n >= 1 && m >= 1 && r >= 1 && r <= kMaxRank && (out || (M && residual)) && (!residual || M),
                 "grace_powersgd_outer: bad arguments");
   const bool vec = (m % 4 == 0) &&
                    (((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(M) |

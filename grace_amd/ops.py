@@ -1128,18 +1128,29 @@ def threshold_compress_strict(x, thr):
 
 
 # ----------------------------------------------------------------------------- PowerSGD
+def _dev_mat(t, what):
+    """A PowerSGD operand the kernels read through its data pointer: on the GPU, float32 and made
+    dense row-major (a transposed or strided view is copied; read as if dense it would be garbage)."""
+    t = require_dev(t, what)
+    if t.dtype != F32:
+        raise TypeError(f"grace_amd: {what} must be float32, got {t.dtype}")
+    return t
+
+
 def powersgd_p(M2d, q):
+    M2d, q = _dev_mat(M2d, "powersgd_p: M"), _dev_mat(q, "powersgd_p: q")
     n, m = M2d.shape
     r = q.shape[1]
     P = torch.empty(n, r, dtype=F32, device=M2d.device)
     ws = workspace("powersgd", _lib.query("grace_powersgd_workspace_bytes", n, m, r), M2d.device)
-    _lib.call("grace_powersgd_p", _p(M2d), n, m, _p(require_dev(q)), r, _p(P), _p(ws), _stream())
+    _lib.call("grace_powersgd_p", _p(M2d), n, m, _p(q), r, _p(P), _p(ws), _stream())
     return P
 
 
 def powersgd_p_draw(M2d, r, seed, out=None):
     """P = M q with q = ops.normal((m, r), seed), drawn inside the contraction (no q buffer);
     out: an n x r f32 view to write P into (a send record)."""
+    M2d = _dev_mat(M2d, "powersgd_p_draw: M")
     n, m = M2d.shape
     P = _out_buf(out.reshape(-1) if out is not None else None, n * r, F32, M2d.device, "powersgd_p_draw").view(n, r)
     ws = workspace("powersgd", _lib.query("grace_powersgd_workspace_bytes", n, m, r), M2d.device)
@@ -1148,11 +1159,12 @@ def powersgd_p_draw(M2d, r, seed, out=None):
 
 
 def powersgd_qt(M2d, P):
+    M2d, P = _dev_mat(M2d, "powersgd_qt: M"), _dev_mat(P, "powersgd_qt: P")
     n, m = M2d.shape
     r = P.shape[1]
     Q = torch.empty(m, r, dtype=F32, device=M2d.device)
     ws = workspace("powersgd", _lib.query("grace_powersgd_workspace_bytes", n, m, r), M2d.device)
-    _lib.call("grace_powersgd_qt", _p(M2d), n, m, _p(require_dev(P)), r, _p(Q), _p(ws), _stream())
+    _lib.call("grace_powersgd_qt", _p(M2d), n, m, _p(P), r, _p(Q), _p(ws), _stream())
     return Q
 
 
@@ -1166,6 +1178,8 @@ def powersgd_w1_ok(M2d, r):
 def powersgd_w1_compress(M2d, q=None, seed=0):
     """World-size-1 rank-4 compress in one pass over M: (P, Q) with P = orthogonalize(M q) and
     Q = M^T P; q is the given [m x 4] matrix, or drawn from `seed` (the ops.normal stream)."""
+    M2d = _dev_mat(M2d, "powersgd_w1_compress: M")
+    q = _dev_mat(q, "powersgd_w1_compress: q") if q is not None else None
     n, m = M2d.shape
     dev = M2d.device
     P = torch.empty(n, 4, dtype=F32, device=dev)
@@ -1173,8 +1187,8 @@ def powersgd_w1_compress(M2d, q=None, seed=0):
     ws = workspace("powersgd_w1", _lib.query("grace_powersgd_w1_workspace_bytes", n, m), dev)
     status = _w1_status(dev)
     _w1_order(dev)
-    _lib.call("grace_powersgd_w1_compress", _p(M2d), n, m, _p(require_dev(q)) if q is not None else None,
-              seed64(seed), _p(P), _p(Q), _p(ws), ws.numel(), status.data_ptr(), _stream())
+    _lib.call("grace_powersgd_w1_compress", _p(M2d), n, m, _p(q), seed64(seed), _p(P), _p(Q), _p(ws), ws.numel(),
+              status.data_ptr(), _stream())
     return P, Q
 
 
@@ -1243,12 +1257,17 @@ def normal_orthogonal(shape, seed, device):
     return A
 
 
-def powersgd_outer(P, Q, M2d=None, want_out=True, want_residual=False):
+def powersgd_outer(P, Q, M2d=None, want_out=True, want_residual=False, out=None, residual=None):
+    """out = P Q^T and / or residual = M - P Q^T; out / residual: n x m f32 buffers to write into
+    (implying want_out / want_residual), else new tensors."""
+    P, Q = _dev_mat(P, "powersgd_outer: P"), _dev_mat(Q, "powersgd_outer: Q")
+    M2d = _dev_mat(M2d, "powersgd_outer: M") if M2d is not None else None
     n, r = P.shape
     m = Q.shape[0]
     dev = P.device
-    out = torch.empty(n, m, dtype=F32, device=dev) if want_out else None
-    res = torch.empty(n, m, dtype=F32, device=dev) if want_residual else None
+    want_out, want_residual = want_out or out is not None, want_residual or residual is not None
+    out = _out_buf(out, n * m, F32, dev, "powersgd_outer").view(n, m) if want_out else None
+    res = _out_buf(residual, n * m, F32, dev, "powersgd_outer (residual)").view(n, m) if want_residual else None
     _lib.call("grace_powersgd_outer", _p(P), _p(Q), n, m, r, _p(out), _p(M2d), _p(res), _stream())
     return out, res
 

@@ -529,6 +529,9 @@ grace_status_t grace_powersgd_qt(const float* M, int64_t n, int64_t m, const flo
 grace_status_t grace_orthogonalize(float* A, int64_t n, int32_t r, void* stream);
 /* q = orthogonalize(normal draws) in one launch (powersgd.py:41-43); same draws as grace_normal_fill */
 grace_status_t grace_normal_orthogonal(float* A, int64_t n, int32_t r, uint64_t seed, void* stream);
+/* out = P Q^T (may be null) and/or residual = M - P Q^T (both null, or both given); r <= 16 like the
+ * contractions (a larger rank is refused, nothing is written).  Per entry the f32 chain
+ * o = 0; o = o + p[c] * q[c], c = 0 .. r-1, each product and sum rounded (no fused multiply-add). */
 grace_status_t grace_powersgd_outer(const float* P, const float* Q, int64_t n, int64_t m, int32_t r, float* out,
                                     const float* M, float* residual, void* stream);
 /* World-size-1 rank-4 compress in one pass over M (replaces the P / orthogonalize / Qt sequence

@@ -2,7 +2,9 @@
 rand32, uniform01x4) -- test infrastructure, not the reference's algorithm (the reference draws from
 torch's generators; rng="torch_cpu" reproduces those).  It lets the device-generator fast paths be
 checked bit for bit: the uniforms a kernel draws on its own equal the ones restated here, so
-``compress(x, seed=s)`` must equal ``compress(x, u=quad_uniforms(...))`` exactly."""
+``compress(x, seed=s)`` must equal ``compress(x, u=quad_uniforms(...))`` exactly.  Also the
+standard normal stream of ops.normal (normal_stream, Box-Muller in float64) and the f32 operation
+chain of the PowerSGD outer product (outer_f32)."""
 import numpy as np
 
 M64 = (1 << 64) - 1
@@ -45,6 +47,64 @@ def quad_uniforms(seed, quad_start, lane):
         h ^= (h << np.uint64(5)) & np.uint64(0xFFFFFFFF)
         out = np.where(lane == j, _to_u01(h), out)
     return out
+
+
+def _mix64_np(z):
+    """mix64 on a uint64 array (the arithmetic wraps modulo 2^64 as on the device)."""
+    z = z + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def normal_stream(seed, n, with_rad=False):
+    """The first n standard normal draws of ops.normal(..., seed) (grace_amd/csrc/powersgd.hip
+    normal_pair): the hash and the two uniforms exactly as the device computes them (integer mix,
+    f32 conversions and f32 multiplies), then Box-Muller in float64 where the device uses its f32
+    hardware log2 / sqrt / sin / cos.  Element e is component e & 1 of pair e >> 1.  with_rad: also
+    the radius sqrt(-2 ln u1) of every element's pair (the scale of the device's rounding error)."""
+    npair = (int(n) + 1) // 2
+    pair = np.arange(npair, dtype=np.uint64)
+    h = _mix64_np(np.uint64(int(seed) & M64) ^ _mix64_np(pair * np.uint64(2) + np.uint64(1)))
+    # 1.0f / 16777217.0f: the f32 literal 16777217 is 2^24 (ties to even), so u1 lies in (0, 1]
+    k1 = np.float32(1.0) / np.float32(16777217.0)
+    u1 = ((h >> np.uint64(40)).astype(np.float32) + np.float32(1.0)) * k1
+    u2 = (h & np.uint64(0xFFFFFF)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    assert u1.dtype == np.float32 and u2.dtype == np.float32
+    rad = np.sqrt(-2.0 * np.log(u1.astype(np.float64)))
+    ang = 2.0 * np.pi * u2.astype(np.float64)
+    z = np.stack([rad * np.cos(ang), rad * np.sin(ang)], axis=1).reshape(-1)[:n]
+    if with_rad:
+        return z, np.repeat(rad, 2)[:n]
+    return z
+
+
+def normal_moment_bounds(z):
+    """The three 5-sigma moment checks of a standard normal sample laid out as Box-Muller pairs:
+    (|mean|, |var - 1|, |corr(z0, z1)|) each divided by its bound -- all must be below 1."""
+    z = np.asarray(z, dtype=np.float64)
+    n = z.size
+    mean, var = z.mean(), z.var()
+    z0, z1 = z[0:n - (n & 1):2], z[1::2]
+    corr = np.mean((z0 - z0.mean()) * (z1 - z1.mean())) / (z0.std() * z1.std())
+    return abs(mean) / (5 / np.sqrt(n)), abs(var - 1) / (5 * np.sqrt(2 / n)), abs(corr) / (5 / np.sqrt(n / 2))
+
+
+NORMAL_SEEDS = (4242, 7)                       # the seeds the normal-stream tests draw with (CPU and GPU)
+NORMAL_ZMAX = np.sqrt(2 * 24 * np.log(2))      # u1 >= 2^-24
+
+
+def outer_f32(P, Q):
+    """P Q^T in the exact f32 operation chain of psgd_outer_kernel / psgd_outer4_kernel (the library
+    is built without fused multiply-add): o = 0, then o = f32(o + f32(p[c] * q[c])) for c = 0..r-1."""
+    P = np.asarray(P, dtype=np.float32)
+    Q = np.asarray(Q, dtype=np.float32)
+    o = np.zeros((P.shape[0], Q.shape[0]), dtype=np.float32)
+    with np.errstate(all="ignore"):
+        for c in range(P.shape[1]):
+            o = o + P[:, c:c + 1] * Q[None, :, c]
+    assert o.dtype == np.float32
+    return o
 
 
 def qsgd_bucket128_uniforms(seed, sizes):

@@ -1,12 +1,47 @@
 """CPU checks of the numpy restatement of the device generator (tests/device_rng.py)."""
 import numpy as np
+import pytest
 
-from tests.device_rng import mix64, qsgd_bucket128_uniforms, quad_uniforms
+from tests.device_rng import (NORMAL_SEEDS, NORMAL_ZMAX, _mix64_np, mix64, normal_moment_bounds, normal_stream, outer_f32,
+                              qsgd_bucket128_uniforms, quad_uniforms)
 
 
 def test_mix64_is_splitmix64():
     # splitmix64's first output from state 0 (the published known answer)
     assert mix64(0) == 0xE220A8397B1DCDAF
+
+
+def test_mix64_array_form_matches_scalar():
+    z = [0, 1, 12345, (1 << 64) - 1, 0x9E3779B97F4A7C15]
+    assert [int(v) for v in _mix64_np(np.array(z, dtype=np.uint64))] == [mix64(v) for v in z]
+
+
+@pytest.mark.parametrize("seed", NORMAL_SEEDS)
+def test_normal_stream_is_standard_normal(seed):
+    n = 1 << 22
+    z = normal_stream(seed, n)
+    assert z.dtype == np.float64 and z.shape == (n,)
+    assert np.isfinite(z).all() and np.abs(z).max() <= NORMAL_ZMAX * (1 + 1e-6)
+    assert max(normal_moment_bounds(z)) < 1, normal_moment_bounds(z)
+    # a prefix of the stream is the stream (element e = component e & 1 of pair e >> 1)
+    assert np.array_equal(normal_stream(seed, 7), z[:7])
+    z2, rad = normal_stream(seed, 9, with_rad=True)
+    assert np.allclose(np.hypot(z2[0:8:2], z2[1:8:2]), rad[0:8:2], rtol=1e-12)
+    assert np.isclose(rad[8], np.hypot(z[8], z[9]), rtol=1e-12)
+
+
+def test_outer_f32_vs_f64():
+    rng = np.random.default_rng(1)
+    for n, m, r in ((37, 1029, 1), (37, 1029, 16), (5, 64, 4), (1, 4, 7)):
+        P = rng.standard_normal((n, r)).astype(np.float32)
+        Q = rng.standard_normal((m, r)).astype(np.float32)
+        o = outer_f32(P, Q)
+        assert o.dtype == np.float32 and o.shape == (n, m)
+        P64, Q64 = P.astype(np.float64), Q.astype(np.float64)
+        assert np.all(np.abs(o - P64 @ Q64.T) <= r * 2.0 ** -24 * (np.abs(P64) @ np.abs(Q64).T))
+    # the chain starts from +0: (-0) * q gives -0, and 0 + (-0) = +0
+    o = outer_f32(np.array([[-0.0]], dtype=np.float32), np.array([[3.0]], dtype=np.float32))
+    assert not np.signbit(o[0, 0])
 
 
 def test_quad_uniforms_range_and_quads():

@@ -42,7 +42,10 @@ def _counters_zero():
     """Arrival / read counters and the run-out count left zero.  Word 0 is the robust path's flag:
     it keeps the tag of the last call that set it (each call waits for its own tag), so it is not
     a counter and is not reset."""
-    ws = ops.workspace("powersgd_w1", 256, torch.device(DEV))
+    # the device as the tensors name it ("cuda:0"): ops.workspace keys its buffers by str(device), and
+    # a bare "cuda" would name a fresh, trivially zero buffer instead of the one the calls used
+    ws = ops.workspace("powersgd_w1", 256, torch.device(DEV, torch.cuda.current_device()))
+    assert ws.numel() > 256 + 2 * 4 * 16384
     head = _np(ws[: 256 + 2 * 4 * 16384].view(torch.int32))
     return not head[1:].any()
 

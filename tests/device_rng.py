@@ -107,12 +107,18 @@ def outer_f32(P, Q):
     return o
 
 
-def qsgd_bucket128_uniforms(seed, sizes):
+def qsgd_bucket128_uniforms(seed, sizes, segs=None):
     """The uniform each element of the segmented QSGD(bucket 128) encoders draws: the quad of element
-    i starts at its bucket's base + 4 * ((i - base) // 4) (grace_amd/csrc/quant.hip)."""
-    starts = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
-    seg = np.repeat(np.arange(len(sizes)), sizes)
-    i = np.arange(int(np.sum(sizes)), dtype=np.int64)
+    i starts at its bucket's base + 4 * ((i - base) // 4) (grace_amd/csrc/quant.hip).
+    segs=(lo, hi): only the draws of segments lo .. hi - 1 (the elements sum(sizes[:lo]) ..
+    sum(sizes[:hi]) - 1), with index arrays over those elements alone."""
+    sizes = np.asarray(sizes, dtype=np.int64)
+    lo, hi = (0, len(sizes)) if segs is None else segs
+    part = sizes[lo:hi]
+    first = int(sizes[:lo].sum())
+    starts = first + np.concatenate([[0], np.cumsum(part)[:-1]]).astype(np.int64)
+    seg = np.repeat(np.arange(len(part)), part)
+    i = first + np.arange(int(part.sum()), dtype=np.int64)
     rel = i - starts[seg]
     base = starts[seg] + (rel // 128) * 128
     qs = base + ((i - base) // 4) * 4

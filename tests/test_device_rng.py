@@ -52,3 +52,16 @@ def test_quad_uniforms_range_and_quads():
     v = qsgd_bucket128_uniforms(7, [5, 130])
     assert np.array_equal(v[5:9], quad_uniforms(7, [5] * 4, np.arange(4)))
     assert np.array_equal(v[133:135], quad_uniforms(7, [133] * 2, np.arange(2)))
+
+
+def test_qsgd_bucket128_uniforms_segment_range():
+    """segs=(lo, hi) gives exactly the full function's draws of those segments: aligned and
+    unaligned starts, partial buckets, one-element segments, the first, the last and no segment."""
+    sizes = [128 * 3, 5, 3, 128 * 2, 130, 1, 15, 256, 7]
+    offs = np.concatenate([[0], np.cumsum(sizes)])
+    full = qsgd_bucket128_uniforms(99, sizes)
+    assert full.size == offs[-1]
+    for lo, hi in [(0, len(sizes)), (0, 1), (1, 4), (2, 3), (4, 9), (8, 9), (5, 5)]:
+        part = qsgd_bucket128_uniforms(99, sizes, segs=(lo, hi))
+        assert part.dtype == np.float32
+        assert np.array_equal(part, full[offs[lo]:offs[hi]]), (lo, hi)

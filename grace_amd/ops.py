@@ -1346,21 +1346,40 @@ def _dgc_sample_top(sample, ks):
     return top, ks
 
 
+def dgc_sample(t, ns, sample_idx=None, seed=0):
+    """(ns,) f32: |t[i_j]| for the ns sample indices of flat f32 device t (grace_dgc_sample) --
+    sample_idx (int64, device, every entry in [0, t.numel())) or, with None, the device generator's
+    draw for `seed`."""
+    t = dev_f32(t)
+    sample = torch.empty(ns, dtype=F32, device=t.device)
+    _lib.call("grace_dgc_sample", _p(t), t.numel(), _p(sample_idx), seed64(seed), ns, _p(sample), _stream())
+    return sample
+
+
+def dgc_sample_comp(g, residual, accum, has_state, momentum, ns, sample_idx=None, seed=0):
+    """dgc_sample of the tensor DgcMemory.compensate would make of gradient g and the memory
+    (residual, accum) -- g itself without state -- read from the state BEFORE compensation
+    (grace_dgc_sample_comp)."""
+    g = dev_f32(g)
+    sample = torch.empty(ns, dtype=F32, device=g.device)
+    _lib.call("grace_dgc_sample_comp", _p(g), _p(residual) if has_state else None,
+              _p(accum) if has_state else None, 1 if has_state else 0, float(momentum), g.numel(), _p(sample_idx),
+              seed64(seed), ns, _p(sample), _stream())
+    return sample
+
+
 def _dgc_sample_top_of(t, ratio, sample_idx, seed, state=None):
-    """The sampling prelude of every DGC entry: draw the 1 % sample of flat t (grace_dgc_sample) --
-    or, with state = (residual, accum, has_state, momentum), of the gradient t compensated from
-    that memory (grace_dgc_sample_comp) -- and take its top by _dgc_sample_top."""
+    """The sampling prelude of every DGC entry: draw the 1 % sample of flat t (dgc_sample) -- or,
+    with state = (residual, accum, has_state, momentum), of the gradient t compensated from that
+    memory (dgc_sample_comp) -- and take its top by _dgc_sample_top."""
     n = t.numel()
     ns = max(1, int(n * 0.01))
     ks = max(1, int(n * ratio * 0.01))
-    sample = torch.empty(ns, dtype=F32, device=t.device)
     if state is None:
-        _lib.call("grace_dgc_sample", _p(t), n, _p(sample_idx), seed64(seed), ns, _p(sample), _stream())
+        sample = dgc_sample(t, ns, sample_idx, seed)
     else:
         residual, accum, has_state, momentum = state
-        _lib.call("grace_dgc_sample_comp", _p(t), _p(residual) if has_state else None,
-                  _p(accum) if has_state else None, 1 if has_state else 0, float(momentum), n, _p(sample_idx),
-                  seed64(seed), ns, _p(sample), _stream())
+        sample = dgc_sample_comp(t, residual, accum, has_state, momentum, ns, sample_idx, seed)
     return _dgc_sample_top(sample, min(ks, ns))
 
 

@@ -437,6 +437,15 @@ def dgc_compress(x, sample_idx, ratio):
     each adjustment is f32(1.3) * thr / f32(0.7) * thr, and the count is compared with the
     Python double 1.3 * numel * ratio in f32 (torch promotes the int64 count with a float
     scalar to the default dtype)."""
+    t, mask, trace = _dgc_adjust(x, sample_idx, ratio)
+    idx = np.nonzero(mask)[0].astype(np.int64)
+    return t[idx].copy(), idx, mask, trace[-1][1]
+
+
+def _dgc_adjust(x, sample_idx, ratio):
+    """dgc_compress's threshold search: (flat t, final mask, trace) where trace lists
+    (move, thr, count) from the sampled threshold (move '') through every adjustment
+    ('U' = thr * 1.3, 'D' = thr * 0.7) in loop order."""
     t = _f32(x).ravel()
     numel = t.size
     s = np.abs(t[np.asarray(sample_idx, dtype=np.int64)]).astype(F32)
@@ -448,19 +457,33 @@ def dgc_compress(x, sample_idx, ratio):
     a = np.abs(t)
     hi = F32(1.3 * numel * ratio)
     lo = F32(0.7 * numel * ratio)
-    mask = a >= thr
-    sel = F32(mask.sum())
-    for _ in range(10):
-        if sel > hi:
-            thr = F32(F32(1.3) * thr)
-        elif sel < lo:
-            thr = F32(F32(0.7) * thr)
-        else:
-            break
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
         mask = a >= thr
         sel = F32(mask.sum())
-    idx = np.nonzero(mask)[0].astype(np.int64)
-    return t[idx].copy(), idx, mask, thr
+        trace = [("", thr, int(mask.sum()))]
+        for _ in range(10):
+            if sel > hi:
+                move, thr = "U", F32(F32(1.3) * thr)
+            elif sel < lo:
+                move, thr = "D", F32(F32(0.7) * thr)
+            else:
+                break
+            mask = a >= thr
+            sel = F32(mask.sum())
+            trace.append((move, thr, int(mask.sum())))
+    return t, mask, trace
+
+
+def dgc_adjust_trace(x, sample_idx, ratio):
+    """The adjustment loop of dgc_compress (dgc.py:24-36) step by step: a list of (move, thr,
+    count), first the sampled threshold with move '', then one entry per adjustment."""
+    return _dgc_adjust(x, sample_idx, ratio)[2]
+
+
+def dgc_adjust_path(x, sample_idx, ratio):
+    """The moves of dgc_compress's adjustment loop as a string of 'U' (thr * 1.3) / 'D'
+    (thr * 0.7); '' when the sampled threshold stands."""
+    return "".join(m for m, _, _ in dgc_adjust_trace(x, sample_idx, ratio))
 
 
 def dgc_memory_compensate(g, residual, accum, momentum):

@@ -3,8 +3,8 @@ rand32, uniform01x4) -- test infrastructure, not the reference's algorithm (the 
 torch's generators; rng="torch_cpu" reproduces those).  It lets the device-generator fast paths be
 checked bit for bit: the uniforms a kernel draws on its own equal the ones restated here, so
 ``compress(x, seed=s)`` must equal ``compress(x, u=quad_uniforms(...))`` exactly.  Also the
-standard normal stream of ops.normal (normal_stream, Box-Muller in float64) and the f32 operation
-chain of the PowerSGD outer product (outer_f32)."""
+standard normal stream of ops.normal (normal_stream, Box-Muller in float64), the f32 operation
+chain of the PowerSGD outer product (outer_f32) and DGC's sample indices (dgc_sample_index)."""
 import numpy as np
 
 M64 = (1 << 64) - 1
@@ -47,6 +47,30 @@ def quad_uniforms(seed, quad_start, lane):
         h ^= (h << np.uint64(5)) & np.uint64(0xFFFFFFFF)
         out = np.where(lane == j, _to_u01(h), out)
     return out
+
+
+def rand32(seed, i):
+    """rand32(seed, i) of common.h on an array of element indices (any below 2^64), as uint64 words
+    below 2^32."""
+    m32 = np.uint64(0xFFFFFFFF)
+    k = mix64(int(seed) & M64)
+    i = np.asarray(i, dtype=np.uint64)
+    h = ((i & m32) * np.uint64(0x9E3779B1)) ^ np.uint64(k & 0xFFFFFFFF) ^ ((i >> np.uint64(32)) * np.uint64(0x7FEB352D))
+    return _fmix32(((h & m32) + np.uint64(k >> 32)) & m32)
+
+
+def dgc_sample_index(seed, j, n):
+    """dgc.hip's dgc_sample_index: the device generator's j-th DGC sample index into n elements,
+    the high 64 bits of (rand32(seed, j) << 32 | rand32(seed ^ 0xD6E8FEB86659FD93, j)) * n.  int64
+    array shaped like j."""
+    n = int(n)
+    hi = rand32(seed, j)
+    lo = rand32((int(seed) & M64) ^ 0xD6E8FEB86659FD93, j)
+    if n < (1 << 32):
+        # (hi 2^32 + lo) n >> 64 in 64-bit words: hi n < 2^64, and the nested floors are exact
+        return ((hi * np.uint64(n) + ((lo * np.uint64(n)) >> np.uint64(32))) >> np.uint64(32)).astype(np.int64)
+    h = hi.astype(object) * (1 << 32) + lo.astype(object)
+    return np.asarray((h * n) // (1 << 64), dtype=object).astype(np.int64)
 
 
 def _mix64_np(z):

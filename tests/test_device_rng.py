@@ -2,8 +2,8 @@
 import numpy as np
 import pytest
 
-from tests.device_rng import (NORMAL_SEEDS, NORMAL_ZMAX, _mix64_np, mix64, normal_moment_bounds, normal_stream, outer_f32,
-                              qsgd_bucket128_uniforms, quad_uniforms)
+from tests.device_rng import (NORMAL_SEEDS, NORMAL_ZMAX, _mix64_np, dgc_sample_index, mix64, normal_moment_bounds,
+                              normal_stream, outer_f32, qsgd_bucket128_uniforms, quad_uniforms, rand32)
 
 
 def test_mix64_is_splitmix64():
@@ -42,6 +42,40 @@ def test_outer_f32_vs_f64():
     # the chain starts from +0: (-0) * q gives -0, and 0 + (-0) = +0
     o = outer_f32(np.array([[-0.0]], dtype=np.float32), np.array([[3.0]], dtype=np.float32))
     assert not np.signbit(o[0, 0])
+
+
+DGC_SEEDS = (0, 123, 2 ** 63 + 5)
+
+
+def test_rand32_matches_quad_uniforms_hash():
+    # uniform01x4's first lane is rand32's top 24 bits
+    e = np.arange(0, 4096, 4)
+    u = (rand32(7, e) >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    assert np.array_equal(u, quad_uniforms(7, e, np.zeros(e.size, dtype=np.int64)))
+
+
+@pytest.mark.parametrize("seed", DGC_SEEDS)
+def test_dgc_sample_index_range_and_uniformity(seed):
+    for n in (1, 99, 100003, 1 << 20, 6553600):
+        ns = max(1, int(n * 0.01))
+        i = dgc_sample_index(seed, np.arange(ns), n)
+        assert i.dtype == np.int64 and i.shape == (ns,)
+        assert i.min() >= 0 and i.max() < n, (seed, n)
+    # the 64-bit word form equals the 128-bit product in Python integers, at n past 2^32 too
+    for n in (99, 6553600, (1 << 32) - 1, (1 << 40) + 7):
+        j = np.array([0, 1, 77, 65535, (1 << 33) + 3], dtype=np.uint64)
+        hi, lo = rand32(seed, j), rand32((seed & ((1 << 64) - 1)) ^ 0xD6E8FEB86659FD93, j)
+        want = [(((int(h) << 32) | int(l)) * n) >> 64 for h, l in zip(hi, lo)]
+        assert dgc_sample_index(seed, j, n).tolist() == want
+    # chi-square over 64 equal bins of [0, n): 63 degrees of freedom, mean 63, sd sqrt(126) = 11.2;
+    # the bound is the mean plus six standard deviations
+    ns, n, bins = 65536, 6553600, 64
+    i = dgc_sample_index(seed, np.arange(ns), n)
+    obs = np.bincount(i // (n // bins), minlength=bins).astype(np.float64)
+    assert obs.size == bins
+    chi2 = float(((obs - ns / bins) ** 2 / (ns / bins)).sum())
+    print(f"seed {seed}: chi-square {chi2:.1f}")
+    assert chi2 <= 130, (seed, chi2)
 
 
 def test_quad_uniforms_range_and_quads():

@@ -59,6 +59,9 @@ SIGNATURES = {
     "grace_topk_carry_size": (I64, [I64, I64]),
     "grace_topk_residual_step_swap": (ST, [P, P, I32, F32, F32, I64, I64, P, P, P, P, I64, I32, P, SZ, P]),
     "grace_topk_residual_step_carry": (ST, [P, P, I32, F32, F32, I64, I64, P, P, P, P, I64, I32, P, I64, P, SZ, P]),
+    "grace_topk_lines_words": (I64, [I64]),
+    "grace_topk_residual_step_lines": (ST, [P, P, I32, F32, F32, I64, I64, P, P, P, P, I64, I32, P, I64, P, I64, P,
+                                            SZ, P]),
     "grace_topk_compress_bf16": (ST, [P, I64, I64, P, P, P, SZ, P]),
     "grace_topk_step_dense_bf16": (ST, [P, I64, I64, P, P, P, P, SZ, P]),
     "grace_topk_residual_step_bf16": (ST, [P, P, I32, F32, F32, I64, I64, P, P, P, P, I64, I32, P, SZ, P]),

@@ -7,6 +7,8 @@ allocates outputs and launches on ``torch.cuda.current_stream()``.
 import functools
 import math
 import os
+import threading
+import weakref
 
 import torch
 
@@ -187,6 +189,21 @@ def reusable_output(slot, shape, dtype, device):
     return buf
 
 
+# _lines_handoff: how a kept output's line map (OUT_LINES, below) travels from the recycler to the
+# step and back without the caller naming it.  take(dense=True) on a hit notes (the tensor, its map
+# or None); the next topk_residual_step of the same thread consumes the note and uses the map only if
+# its `out` IS that tensor -- the buffer whose previous step wrote the map, unmodified (unheld()) --
+# and notes (the tensor, the map it used); keep() of that very tensor stores the map in its entry.
+# Every other order of calls drops the note and with it the map: the step then writes every line,
+# which is always correct.  Per thread, weak references only.
+class _LinesNote(threading.local):
+    taken = None      # (weakref of the tensor a dense hit handed out, its line map or None)
+    written = None    # (weakref of the tensor the last step wrote with a line map, that map)
+
+
+_lines = _LinesNote()
+
+
 class OutputRecycler:
     """Per-name recycled dense outputs of the world-1 top-k step.  A step's result is zero except at
     its payload positions; when the caller has dropped it (no tensor or view of its storage left
@@ -206,13 +223,17 @@ class OutputRecycler:
         """(out tensor, prev_idx or None) for the next step of `name` shaped like `like` (a tensor, or
         a (numel, device) pair for an f32 vector).  A miss allocates (torch.empty_like) unless
         alloc=False, which returns (None, None) and leaves the allocation to the caller.  dense=True:
-        the caller rewrites every element (the buffer is kept for its placement, not to skip
-        writes); such hits are counted in dense_hits."""
+        the caller defines every element (the buffer is kept for its placement and for its line
+        map, not for its payload positions); such hits are counted in dense_hits.  A dense hit also
+        hands the buffer's line map on to the step that is about to write it (_lines_handoff): the
+        next topk_residual_step of this thread, if it is given this very tensor as its output."""
         numel, device = (like.numel(), like.device) if isinstance(like, torch.Tensor) else (int(like[0]), like[1])
-        hit = self._hit.pop(name, None)   # park(out, versioned) + (prev_idx, key)
+        hit = self._hit.pop(name, None)   # park(out, versioned) + (prev_idx, key, lines)
+        _lines.taken = _lines.written = None
         if hit is not None and hit[5] == (numel, torch.device(device), _stream()) and unheld(hit):
             if dense:
                 self.dense_hits += 1
+                _lines.taken = (weakref.ref(hit[0]), hit[6])   # (weak: unheld() counts references)
             else:
                 self.hits += 1
             return hit[0], hit[4]
@@ -223,9 +244,14 @@ class OutputRecycler:
             return torch.empty_like(like), None
         return torch.empty(numel, dtype=F32, device=device), None
 
-    def keep(self, name, out, idx):
-        """Remember this step's result and its payload indices (int32, length k)."""
-        self._hit[name] = park(out, versioned=True) + (idx, (out.numel(), out.device, _stream()))
+    def keep(self, name, out, idx, lines=None):
+        """Remember this step's result and its payload indices (int32, length k), and beside them
+        the line map the step left for `out`: `lines`, or the one the step that has just written this
+        very tensor used (_lines_handoff); None where the step had none."""
+        w, _lines.written = _lines.written, None
+        if lines is None and w is not None and w[0]() is out:
+            lines = w[1]
+        self._hit[name] = park(out, versioned=True) + (idx, (out.numel(), out.device, _stream()), lines)
 
     def drop(self, name):
         """Forget `name`'s previous result (its next step allocates and writes densely)."""
@@ -427,7 +453,7 @@ def topk_workspace(n, k, device):
 # (profiles/r06_place4_5.txt).  At a large bucket's first step, pick_pair tries a few residual and
 # output allocations against the step's gradient with the pass's own streaming skeleton
 # (grace_topk_stream_probe) and keeps the fastest pair; the output buffer then stays with the name
-# (the dropped previous result comes back and is rewritten densely).  One host synchronisation per
+# (the dropped previous result comes back, with its line map: OUT_LINES).  One host synchronisation per
 # name; GRACE_PLACE_PROBE=0 turns it off.
 PLACE_PROBE = os.environ.get("GRACE_PLACE_PROBE", "1") != "0"
 PLACE_MIN_N = 1 << 24
@@ -542,9 +568,29 @@ def topk_step_dense(x, k, out=None, prev_idx=None):
     return buf, vals, idx, out
 
 
+# Line-skipping dense output: the world-1 f32 residual step stores only the 64-B lines
+# of a KEPT output buffer that can be non-zero in this step or were in the previous one
+# (grace_topk_residual_step_lines).  False: the same engine on the same buffers writes every line
+# (the A/B switch, tools/ab_out_lines.py); a map not passed for a step is dropped, so the first
+# step after switching back on writes every line once.
+OUT_LINES = True
+
+
+def topk_lines_map(n, device):
+    """A fresh (invalid: all zero) line map for an n-element kept output, or None where the step
+    has none."""
+    words = int(_lib.query("grace_topk_lines_words", n))
+    return torch.zeros(words, dtype=torch.int64, device=device) if words else None
+
+
 def topk_residual_step(g, residual, has_residual, beta, gamma, k, out=None, payload=None, carry=None,
-                       carry_valid=False, prev_idx=None):
-    """carry: f32[topk_carry_size(n, k)] kept with `residual` (grace_topk_residual_step_carry);
+                       carry_valid=False, prev_idx=None, lines=None):
+    """lines: the line map kept beside `out` (topk_lines_map; `out` must be the buffer the map's
+    previous step wrote, unmodified, or the map fresh): only the lines of `out` that can be non-zero
+    now or were in that step are stored, the result is the dense step's bit for bit.  Without
+    `lines`, an `out` that OutputRecycler.take(dense=True) has just handed back on a hit brings its
+    own map (_lines_handoff; a fresh one on its first hit) while OUT_LINES is on.
+    carry: f32[topk_carry_size(n, k)] kept with `residual` (grace_topk_residual_step_carry);
     carry_valid: it holds the samples the previous step of this residual wrote.  prev_idx: int32
     payload indices of the earlier step whose result `out` still holds unmodified (a recycled
     output: the step zeroes those and writes only its own selection).  A bfloat16 g
@@ -552,6 +598,13 @@ def topk_residual_step(g, residual, has_residual, beta, gamma, k, out=None, payl
     there is no recycled output."""
     g = dev_grad(g)
     n = g.numel()
+    taken, _lines.taken, _lines.written = _lines.taken, None, None   # consumed by this step, whatever it is
+    if (lines is None and taken is not None and out is not None and taken[0]() is out and OUT_LINES
+            and has_residual and prev_idx is None and g.dtype == F32):
+        # a kept buffer on its first hit gets a fresh (invalid) map: this step writes every line
+        lines = taken[1] if taken[1] is not None else topk_lines_map(n, g.device)
+        if lines is not None:
+            _lines.written = (taken[0], lines)
     buf, vals, idx = new_payload(k, g.device) if payload is None else payload
     ws = topk_workspace(n, k, g.device)
     if carry is not None and (carry.dtype != F32 or not carry.is_contiguous()):
@@ -570,7 +623,13 @@ def topk_residual_step(g, residual, has_residual, beta, gamma, k, out=None, payl
         return buf, vals, idx
     if prev_idx is not None and (out is None or prev_idx.dtype != torch.int32 or not prev_idx.is_contiguous()):
         raise ValueError("grace_amd: prev_idx needs an output and contiguous int32 indices")
-    if carry is None and prev_idx is None:
+    if lines is not None:
+        if prev_idx is not None or out is None or lines.dtype != torch.int64 or not lines.is_contiguous():
+            raise ValueError("grace_amd: a line map needs an output, no prev_idx and a contiguous int64 tensor")
+        _lib.call("grace_topk_residual_step_lines", _p(g), _p(residual), 1 if has_residual else 0, float(beta),
+                  float(gamma), n, k, _p(vals), _p(idx), _p(out), _p(carry), carry.numel() if carry is not None else 0,
+                  1 if carry_valid else 0, None, 0, _p(lines), lines.numel(), _p(ws), ws.numel(), _stream())
+    elif carry is None and prev_idx is None:
         _lib.call("grace_topk_residual_step", _p(g), _p(residual), 1 if has_residual else 0, float(beta),
                   float(gamma), n, k, _p(vals), _p(idx), _p(out), _p(ws), ws.numel(), _stream())
     else:

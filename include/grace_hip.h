@@ -48,8 +48,10 @@ grace_status_t grace_read_status(const void* workspace, int32_t* status_host, vo
 
 /* The streaming skeleton of the headline main pass (bench.py's HBM ceiling): topk_main with the
  * same chunking, loads, stores and grid, but no classification -- r' = r + g and (sparse == 0)
- * out = 0 written in place; sparse != 0 is the recycled-output layout (out untouched).  Its rate
- * is the ceiling of the real pass's exact memory layout. */
+ * out = 0 written in place; sparse == 1 is the recycled-output layout (out untouched).  Its rate
+ * is the ceiling of the real pass's exact memory layout.  sparse == 2 / 3 / 4: the line-skipping
+ * ceilings -- out stored only in a hashed 0.52 / 0.31 / 0.17 of its 128-B / 64-B / 32-B lines (8 /
+ * 4 / 2 lanes of a wave store switched together), g, r, r' as before. */
 size_t grace_topk_stream_probe_workspace_bytes(int64_t n);
 /* Plain device allocations for the buffer-pair placement probe's spacers (grace_amd/ops.py
  * pick_pair): hipMalloc / hipFree, so the caller's allocator cache holds none of it.  A failed
@@ -220,6 +222,23 @@ grace_status_t grace_topk_residual_step_carry(const float* g, float* residual, i
                                               int32_t* idx, float* out, float* carry, int64_t carry_len,
                                               int32_t carry_valid, const int32_t* prev_idx, int64_t prev_count,
                                               void* ws, size_t ws_bytes, void* stream);
+/* grace_topk_residual_step_carry with the line map of a KEPT dense output: `out` is the buffer
+ * this map's previous step wrote, unmodified since (or any buffer with a map whose word 0 is 0), and
+ * `lines` (u64[lines_len >= grace_topk_lines_words(n)], 128-B aligned, zero before its first use,
+ * kept by the caller beside `out`) records which 64-B lines of `out` may be non-zero.  The f32
+ * step with a residual on the large path then stores only the lines of `out` that can be non-zero
+ * now or were in the previous step; every other line holds +0 and stays +0, so the result is the
+ * dense step's bit for bit.  A step that leaves the fast path (exact fallback), or any other path
+ * handed a map (no residual, k >= n, prev_idx), writes `out` as without one and marks the map
+ * invalid: the next step writes every line.  lines NULL: grace_topk_residual_step_carry.
+ * grace_topk_lines_words: u64 words of the map for n elements, 0 where the step has none. */
+int64_t grace_topk_lines_words(int64_t n);
+grace_status_t grace_topk_residual_step_lines(const float* g, float* residual, int32_t has_residual,
+                                              float beta, float gamma, int64_t n, int64_t k, float* vals,
+                                              int32_t* idx, float* out, float* carry, int64_t carry_len,
+                                              int32_t carry_valid, const int32_t* prev_idx, int64_t prev_count,
+                                              uint64_t* lines, int64_t lines_len, void* ws, size_t ws_bytes,
+                                              void* stream);
 /* zeros(n).scatter_(idx, vals)  (topk.py:45-49; threshold.py:25-26; randomk.py:39-40). */
 grace_status_t grace_sparse_decode(const float* vals, const int32_t* idx, int64_t count, float* out,
                                    int64_t n, void* stream);

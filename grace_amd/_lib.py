@@ -26,6 +26,7 @@ SIGNATURES = {
     "grace_status_take": (ctypes.c_int32, [P]),
     "grace_topk_status_word": (ST, [P]),
     "grace_topk_fallback_spin_limit": (ctypes.c_int64, [ctypes.c_int64]),
+    "grace_topk_main_grid_limit": (ctypes.c_uint32, [ctypes.c_uint32]),
     "grace_topk_stream_probe_workspace_bytes": (SZ, [I64]),
     "grace_topk_stream_probe": (ST, [P, P, P, I64, I32, P, SZ, P]),
     "grace_spacer_alloc": (ST, [SZ, P]),
@@ -206,6 +207,29 @@ def load():
 
 
 _fns = {}
+
+
+def use(path):
+    """Make the build of the library at `path` the one every later call goes to, and return its
+    handle (tools that A/B two builds in one process).  An older build may lack newer symbols: those
+    stay unbound and raise AttributeError only if called."""
+    global _lib
+    with _lock:
+        lib = _handles.get(path)
+        if lib is None:
+            lib = ctypes.CDLL(os.path.abspath(path))
+            for name, (res, args) in SIGNATURES.items():
+                f = getattr(lib, name, None)
+                if f is not None:
+                    f.restype = res
+                    f.argtypes = args
+            _handles[path] = lib
+        _lib = lib
+        _fns.clear()
+    return lib
+
+
+_handles = {}
 
 
 def call(name, *args):

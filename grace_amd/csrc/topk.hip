@@ -948,9 +948,15 @@ __device__ __forceinline__ uint32_t classify_group(const StepArgs& a, const Topk
 }
 
 // The staged list of one chunk leaves: the waves' regions are concatenated; one pass counts sure /
-// candidate entries with wave ballots, one reservation per list and chunk, a second pass writes them
-// (wave ballot ranks, one LDS add per wave and list); candidates are counted into the LDS histogram
-// there
+// candidate entries with wave ballots, ONE reservation per chunk for both lists, a second pass
+// writes them (wave ballot ranks, one LDS add per wave and list); candidates are counted into the
+// LDS histogram there.
+// n_sure and n_cand are one 8-B-aligned word, reserved together by one returning 64-bit add of
+// ns | nc << 32 (n_sure <= n < 2^31 never carries into n_cand): one round trip to the memory side
+// per chunk where two dependent ones were.  Every other user keeps the 32-bit words.  The result is
+// used inside thread 0's branch: its wait (vmcnt(0), which also drains the wave's trailing stores)
+// then sits in that branch, which the other three waves skip.
+static_assert(offsetof(TopkCtl, n_sure) == 16 && offsetof(TopkCtl, n_cand) == 20, "one 8-B word: n_sure | n_cand << 32");
 template <bool SPARSE_OUT = false>
 __device__ __forceinline__ void flush_staged(const StepArgs& a, const TopkWs& w, MainShared& sm, uint32_t lo,
                                              uint32_t hi, uint32_t sh, uint32_t mid, uint32_t wfill) {
@@ -981,10 +987,14 @@ __device__ __forceinline__ void flush_staged(const StepArgs& a, const TopkWs& w,
   __syncthreads();
   if (tid == 0) {
     const uint32_t c = sm.cnt[0], ns = c & 0xFFFFu, nc = c >> 16;
-    // one reservation per chunk and list (5461 per step on each counter: as 8 copies, a timing-only
-    // build, the main pass was 2 us faster in 196 -- within the spread, so the one counter stays)
-    sm.gbase[0] = ns ? atomicAdd(&w.ctl->n_sure, ns) : 0u;
-    sm.gbase[1] = nc ? atomicAdd(&w.ctl->n_cand, nc) : 0u;
+    // one reservation per chunk (5461 per step: as 8 copies of the counters, a timing-only build,
+    // the main pass was 2 us faster in 196 -- within the spread, so the one word stays)
+    unsigned long long base = 0;
+    if (c)
+      base = atomicAdd(reinterpret_cast<unsigned long long*>(&w.ctl->n_sure),
+                       (unsigned long long)ns | ((unsigned long long)nc << 32));
+    sm.gbase[0] = (uint32_t)base;
+    sm.gbase[1] = (uint32_t)(base >> 32);
     sm.cnt[0] = 0u;
     sm.cnt[1] = 0u;
   }
@@ -1870,11 +1880,21 @@ __global__ __launch_bounds__(256) void topk_all(StepArgs a) {
 constexpr int kNoresBigVec = 64;
 constexpr int64_t kNoresBigMinN = (int64_t)1024 * kMainBlock * 4 * kNoresBigVec;   // 2^26 at 64
 
+// The main pass's grid for `nchunks` chunks: one chunk per workgroup, unless
+// grace_topk_main_grid_limit caps it (tests: several chunks per workgroup on a small bucket; every
+// pass has the grid-stride loop).  Capped grids with a cross-chunk prefetch were measured and are not
+// faster (DESIGN §4 "One reservation per chunk").
+static uint32_t g_main_grid_limit = 0;   // 0: no cap
+static unsigned main_grid(int64_t nchunks) {
+  const int64_t lim = g_main_grid_limit ? (int64_t)g_main_grid_limit : nchunks;
+  return (unsigned)(nchunks < lim ? nchunks : lim);
+}
+
 // the main pass at NV float4 per lane per chunk (one chunk per workgroup)
 template <bool HAS_RES, int MODE, int NV, typename E = float>
 static void launch_main(const StepArgs& a, const TopkWs& w, bool sparse, bool vec, hipStream_t s) {
   constexpr int64_t kCh = (int64_t)kMainBlock * 4 * NV;
-  const unsigned nblk = (unsigned)((a.n + kCh - 1) / kCh);
+  const unsigned nblk = main_grid((a.n + kCh - 1) / kCh);
   if (sparse) {
     if constexpr (kWritesOut<MODE> && !kIsBf16<E>) {
       if (vec)
@@ -2392,6 +2412,12 @@ int32_t grace_status_take(int32_t* host_word) {
 grace_status_t grace_topk_status_word(int32_t* host_word) {
   g_topk_hstatus = host_word;
   return GRACE_OK;
+}
+
+uint32_t grace_topk_main_grid_limit(uint32_t limit) {
+  const uint32_t prev = g_main_grid_limit;
+  g_main_grid_limit = limit;
+  return prev;
 }
 
 int64_t grace_topk_fallback_spin_limit(int64_t limit) {

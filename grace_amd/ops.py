@@ -442,6 +442,13 @@ def topk_fallback_spin_limit(limit=-1):
     return int(_lib.query("grace_topk_fallback_spin_limit", int(limit)))
 
 
+def topk_main_grid_limit(limit):
+    """Cap the top-k main pass's grid at `limit` workgroups (0, the default: one chunk per workgroup),
+    process-wide; results do not depend on it (tests run several chunks per workgroup on small
+    buckets).  Returns the previous limit."""
+    return int(_lib.query("grace_topk_main_grid_limit", int(limit)))
+
+
 def topk_workspace(n, k, device):
     _topk_status()
     return workspace("topk", _lib.query("grace_topk_workspace_bytes", n, k), device)

@@ -79,6 +79,12 @@ int32_t grace_status_take(int32_t* host_word);
 grace_status_t grace_topk_status_word(int32_t* host_word);
 int64_t grace_topk_fallback_spin_limit(int64_t limit);
 
+/* Cap of the top-k main pass's grid, process-global: at most `limit` workgroups, each taking every
+ * limit-th chunk of the bucket (0, the default: no cap, one chunk per workgroup).  Results do not
+ * depend on it; tests set 1 - 3 so that a small bucket runs several chunks in one workgroup.
+ * Returns the previous limit. */
+uint32_t grace_topk_main_grid_limit(uint32_t limit);
+
 /* Event timer on the kernel's own stream, used by bench.py to time the dominant kernel of a
  * fused step: when enabled, that kernel's launch is bracketed by hipEventRecord. */
 grace_status_t grace_timer_enable(int enable);

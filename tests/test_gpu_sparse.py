@@ -342,11 +342,13 @@ def test_randomk_world1_fused_step_equals_unfused(n, rng):
     assert np.count_nonzero(fo[-1]) > 0
 
 
-@pytest.mark.parametrize("n,ratio", [((1 << 24) + 5, 0.01), (100003, 0.7), (8192, 0.3)])
+@pytest.mark.parametrize("n,ratio", [((1 << 24) + 5, 0.01), (100003, 0.7), (8192, 0.3),
+                                     ((1 << 26) + 8192 + 5, 0.0001)])
 def test_randomk_dense_step_equals_three_launch_step(n, ratio):
     """grace_randomk_step_w1_dense (indices grouped by chunk, one streaming pass) against
     grace_randomk_step_w1 (pass + gather + scatter): out and r' bit-identical, with many duplicate
-    indices (ratio 0.7), special values and a partial last chunk."""
+    indices (ratio 0.7), special values, a partial last chunk, and more chunks (8194) than one round
+    of the grouping's scan of the chunk counts covers."""
     from grace_amd import ops as G
     rng = np.random.default_rng(n)
     g0 = rng.standard_normal(n).astype(np.float32)

@@ -13,6 +13,8 @@
 // grouped payload carries each entry's offset inside its chunk as a u16 (13 bits) instead of the
 // int32 index: 6 B per entry on the wire instead of 8.
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace grace {
@@ -172,14 +174,22 @@ __global__ __launch_bounds__(kGroupBlock) void group_scatter_kernel(const float*
 // SMALLW (world <= 64): every wave keeps the ranks' bounds in registers (lane w holds rank w's,
 // read with readlane), so the tile is the workgroup's only LDS -- 32 KB, five workgroups per CU
 // instead of four with the 8 KB bounds table beside it.
+// OutT: float, or uint16_t for a bfloat16 result (grace_sparse_aggregate_sorted_bf16).  Only the
+// epilogue differs: the f32 sum is divided in f32 and rounded once to bf16 in integer arithmetic
+// (common.h f32_to_bf16, not the hardware convert: DESIGN.md §9), 2 B per element written instead
+// of the 4 + 4 + 2 of the f32 decode followed by grace_f32_to_bf16.  The tile and the launch bounds
+// are the f32 kernel's, so the occupancy above holds for the bf16 instantiations as well.
 constexpr int kRankBatch = 8;
 constexpr int kMaxRanks = 1024;
-template <bool SMALLW>
+// bf16 results a lane stores at once: one 16-B non-temporal store (A/B against 4 results, 8 B, the
+// f32 epilogue's mapping; 2^26 elements, W = 8: 56.1 us against 59.9, profiles/bf16_decode.txt)
+constexpr int kBf16Lane = 8;
+template <bool SMALLW, typename OutT>
 __global__ __launch_bounds__(kPBlock) void chunk_accumulate_kernel(const float* __restrict__ vals,
                                                                   const uint16_t* __restrict__ off,
                                                                   const int32_t* __restrict__ ends, int64_t stride,
                                                                   int world, float divisor,
-                                                                  float* __restrict__ out, int64_t n) {
+                                                                  OutT* __restrict__ out, int64_t n) {
   __shared__ float tile[kPChunk];
   __shared__ int32_t s_b[SMALLW ? 1 : 2 * kMaxRanks];
   const int t = threadIdx.x;
@@ -240,16 +250,37 @@ __global__ __launch_bounds__(kPBlock) void chunk_accumulate_kernel(const float* 
       __syncthreads();
     }
   }
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  if (c0 + kPChunk <= n && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
-    for (int e = t * 4; e < kPChunk; e += kPBlock * 4) {
-      f4 q = {tile[e], tile[e + 1], tile[e + 2], tile[e + 3]};
-      if (divisor != 1.0f) { q.x = q.x / divisor; q.y = q.y / divisor; q.z = q.z / divisor; q.w = q.w / divisor; }
-      __builtin_nontemporal_store(q, reinterpret_cast<f4*>(out + c0 + e));
+  if constexpr (std::is_same<OutT, float>::value) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    if (c0 + kPChunk <= n && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
+      for (int e = t * 4; e < kPChunk; e += kPBlock * 4) {
+        f4 q = {tile[e], tile[e + 1], tile[e + 2], tile[e + 3]};
+        if (divisor != 1.0f) { q.x = q.x / divisor; q.y = q.y / divisor; q.z = q.z / divisor; q.w = q.w / divisor; }
+        __builtin_nontemporal_store(q, reinterpret_cast<f4*>(out + c0 + e));
+      }
+    } else {
+      for (int e = t; e < kPChunk && c0 + e < n; e += kPBlock)
+        out[c0 + e] = divisor != 1.0f ? tile[e] / divisor : tile[e];
     }
   } else {
-    for (int e = t; e < kPChunk && c0 + e < n; e += kPBlock)
-      out[c0 + e] = divisor != 1.0f ? tile[e] / divisor : tile[e];
+    // bf16 bits: the sum is divided in f32 and rounded once (common.h f32_to_bf16)
+    static_assert(std::is_same<OutT, uint16_t>::value, "out is float or bf16 bits");
+    typedef uint32_t uv __attribute__((ext_vector_type(kBf16Lane / 2)));
+    if (c0 + kPChunk <= n && (reinterpret_cast<uintptr_t>(out) & (2u * kBf16Lane - 1u)) == 0) {
+      for (int e = t * kBf16Lane; e < kPChunk; e += kPBlock * kBf16Lane) {
+        uv p;
+#pragma unroll
+        for (int j = 0; j < kBf16Lane / 2; ++j) {
+          float a = tile[e + 2 * j], b = tile[e + 2 * j + 1];
+          if (divisor != 1.0f) { a = a / divisor; b = b / divisor; }
+          p[j] = pack_bf16x2(a, b);
+        }
+        __builtin_nontemporal_store(p, reinterpret_cast<uv*>(out + c0 + e));
+      }
+    } else {
+      for (int e = t; e < kPChunk && c0 + e < n; e += kPBlock)
+        out[c0 + e] = f32_to_bf16(divisor != 1.0f ? tile[e] / divisor : tile[e]);
+    }
   }
 }
 
@@ -314,12 +345,30 @@ grace_status_t grace_sparse_aggregate_sorted(const float* vals, const uint16_t* 
                 "grace_sparse_aggregate_sorted: bad arguments (1 <= world <= 1024, n <= 2^28)");
   const int64_t nchunks = (n + kPChunk - 1) / kPChunk;
   if (world <= kWave)
-    chunk_accumulate_kernel<true><<<(unsigned)nchunks, kPBlock, 0, as_stream(stream)>>>(
+    chunk_accumulate_kernel<true, float><<<(unsigned)nchunks, kPBlock, 0, as_stream(stream)>>>(
         vals, off, reinterpret_cast<const int32_t*>(ends), stride, world, divisor, out, n);
   else
-    chunk_accumulate_kernel<false><<<(unsigned)nchunks, kPBlock, 0, as_stream(stream)>>>(
+    chunk_accumulate_kernel<false, float><<<(unsigned)nchunks, kPBlock, 0, as_stream(stream)>>>(
         vals, off, reinterpret_cast<const int32_t*>(ends), stride, world, divisor, out, n);
   GRACE_CHECK_LAUNCH("grace_sparse_aggregate_sorted");
+  return GRACE_OK;
+}
+
+// the same aggregate with the result rounded once to bfloat16 (out holds bf16 bits)
+grace_status_t grace_sparse_aggregate_sorted_bf16(const float* vals, const uint16_t* off, const uint32_t* ends,
+                                                  int64_t stride, int32_t world, float divisor, uint16_t* out,
+                                                  int64_t n, void* stream) {
+  GRACE_REQUIRE(vals && off && ends && out && world >= 1 && world <= kMaxRanks && n >= 1 &&
+                    (n + kPChunk - 1) / kPChunk <= kMaxGroupChunks,
+                "grace_sparse_aggregate_sorted_bf16: bad arguments (1 <= world <= 1024, n <= 2^28)");
+  const int64_t nchunks = (n + kPChunk - 1) / kPChunk;
+  if (world <= kWave)
+    chunk_accumulate_kernel<true, uint16_t><<<(unsigned)nchunks, kPBlock, 0, as_stream(stream)>>>(
+        vals, off, reinterpret_cast<const int32_t*>(ends), stride, world, divisor, out, n);
+  else
+    chunk_accumulate_kernel<false, uint16_t><<<(unsigned)nchunks, kPBlock, 0, as_stream(stream)>>>(
+        vals, off, reinterpret_cast<const int32_t*>(ends), stride, world, divisor, out, n);
+  GRACE_CHECK_LAUNCH("grace_sparse_aggregate_sorted_bf16");
   return GRACE_OK;
 }
 

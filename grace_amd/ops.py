@@ -792,11 +792,16 @@ def sort_payload(buf, k, n):
     return out
 
 
-def sparse_aggregate_sorted(gathered, k, world, n, divisor):
-    """Rank-ordered aggregate of W chunk-grouped payloads (rank-major, stride sorted_payload_len)."""
-    out = torch.empty(n, dtype=F32, device=gathered.device)
+def sparse_aggregate_sorted(gathered, k, world, n, divisor, out_dtype=F32):
+    """Rank-ordered aggregate of W chunk-grouped payloads (rank-major, stride sorted_payload_len).
+    out_dtype=torch.bfloat16: the same f32 sum and division rounded once to bf16 in the decode's
+    epilogue (grace_sparse_aggregate_sorted_bf16)."""
+    if out_dtype != F32 and out_dtype != BF16:
+        raise TypeError(f"grace_amd: sparse_aggregate_sorted writes float32 or bfloat16, got {out_dtype}")
+    out = torch.empty(n, dtype=out_dtype, device=gathered.device)
     stride = sorted_payload_len(k, n)
-    _lib.call("grace_sparse_aggregate_sorted", _p(gathered), _p(gathered[k:]), _p(gathered[k + _off_words(k):]),
+    _lib.call("grace_sparse_aggregate_sorted_bf16" if out_dtype == BF16 else "grace_sparse_aggregate_sorted",
+              _p(gathered), _p(gathered[k:]), _p(gathered[k + _off_words(k):]),
               stride, int(world), float(divisor), _p(out), int(n), _stream())
     return out
 

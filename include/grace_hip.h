@@ -268,6 +268,12 @@ grace_status_t grace_sort_payload(const float* vals, const int32_t* idx, int64_t
 grace_status_t grace_sparse_aggregate_sorted(const float* vals, const uint16_t* off, const uint32_t* ends,
                                              int64_t stride, int32_t world, float divisor, float* out, int64_t n,
                                              void* stream);
+/* grace_sparse_aggregate_sorted with a bfloat16 result (out holds bf16 bits): the same rank-ordered
+ * f32 sum and f32 division, rounded once to nearest even as grace_f32_to_bf16 rounds (a NaN stays a
+ * NaN), 2 B per element written.  Same limits. */
+grace_status_t grace_sparse_aggregate_sorted_bf16(const float* vals, const uint16_t* off, const uint32_t* ends,
+                                                  int64_t stride, int32_t world, float divisor, uint16_t* out,
+                                                  int64_t n, void* stream);
 /* as grace_sparse_aggregate with `out` already zero-filled by the caller (lets the fill overlap
  * the payload exchange); 1 <= world <= 64 */
 grace_status_t grace_sparse_aggregate_into(const float* vals, const int32_t* idx, int64_t stride,

@@ -74,6 +74,9 @@ SIGNATURES = {
     "grace_topk_segmented_fin_blocks": (I32, [I64, I64]),
     "grace_topk_segmented_step": (ST, [P, P, I32, F32, F32, P, P, P, I32, P, I32, P, P, I64, P, P, P, I64, I64, P, P, P,
                                        P, P, I32, P, SZ, I64, P]),
+    "grace_topk_segmented_chunk_bf16": (I64, [I32, I32]),
+    "grace_topk_segmented_step_bf16": (ST, [P, P, I32, F32, F32, P, P, P, I32, P, I32, P, P, I64, P, P, P, I64, I64, P,
+                                            P, P, P, P, I32, P, SZ, I64, P]),
     "grace_topk_segmented_workspace_bytes": (I64, [P, P, I32]),
     "grace_topk_segmented_carry_len": (I64, [I64]),
     "grace_shard_record_words": (SZ, [I64]),

@@ -85,9 +85,10 @@ template <bool HAS_RES, int MODE, typename E = float>
 constexpr int kVecOf = kIsBf16<E> ? (HAS_RES ? kMainVec12B : kMainVecNoRes)
                        : kBytesOf<HAS_RES, MODE> >= 16 ? kMainVec
                        : (kBytesOf<HAS_RES, MODE> >= 12 ? kMainVec12B : kMainVecNoRes);
-// (f32 only: its users -- the segmented kernels, the stream probe, grace_topk_segmented_chunk -- have
-// no bf16 form; a bf16 pass's chunk is kMainBlock * 4 * kVecOf<HAS_RES, MODE, E>, in run_topk)
-template <bool HAS_RES, int MODE> constexpr int kChunkOf = kMainBlock * 4 * kVecOf<HAS_RES, MODE>;
+// (the segmented kernels and grace_topk_segmented_chunk[_bf16] take it per element type; the stream
+// probe is f32 only, and run_topk spells a bf16 pass's chunk out itself)
+template <bool HAS_RES, int MODE, typename E = float>
+constexpr int kChunkOf = kMainBlock * 4 * kVecOf<HAS_RES, MODE, E>;
 // bf16 world-1 residual step (kDenseFused): the f32 pass parks t of a provisional pick in `out` and
 // writes r' = t - t at once, and its exact fallback reads t back from there.  A bf16 `out` holds t
 // rounded, so this pass leaves t in r everywhere (as kDenseRes does) and the finalize zeroes the k
@@ -2057,7 +2058,7 @@ constexpr int kSegSmallMax = 8192;
 static_assert(kSegSmallMax <= kSmallN, "small segments fit the prep workgroup");
 
 struct SegPlan {
-  const float* g;
+  const float* g;      // (bf16: the uint16_t buffers in the float-typed g / out fields, as StepArgs)
   float* r;
   float* out;          // dense world-1 output (kDenseFused) or null (kDenseRes)
   float* vals;
@@ -2083,10 +2084,12 @@ struct SegPlan {
   int32_t carry_valid;
 };
 
+// E: g and out are offset in units of E (kernels read them through g_of<E> / out_of<E>)
+template <typename E = float>
 __device__ __forceinline__ StepArgs seg_step_args(const SegPlan& p, int s) {
   const int64_t o = p.seg_off[s], ko = p.k_off[s];
   StepArgs a{};
-  a.g = p.g + o;
+  a.g = reinterpret_cast<const float*>(reinterpret_cast<const E*>(p.g) + o);
   a.r = p.r + o;
   a.r_in = a.r;
   a.beta = p.beta;
@@ -2095,7 +2098,7 @@ __device__ __forceinline__ StepArgs seg_step_args(const SegPlan& p, int s) {
   a.k = p.k_off[s + 1] - ko;
   a.vals = p.vals + ko;
   a.idx = p.idx + ko;
-  a.out = p.out ? p.out + o : nullptr;
+  a.out = p.out ? reinterpret_cast<float*>(reinterpret_cast<E*>(p.out) + o) : nullptr;
   a.idx_base = o;
   return a;
 }
@@ -2127,8 +2130,9 @@ __host__ __device__ __forceinline__ int64_t seg_sample_n(int64_t n) {
   return S < n / 4 ? S : n / 4;
 }
 // the step arguments of large segment slot li, with its carry (prep and finalize)
+template <typename E = float>
 __device__ __forceinline__ StepArgs seg_large_args(const SegPlan& p, int li) {
-  StepArgs a = seg_step_args(p, p.large[li]);
+  StepArgs a = seg_step_args<E>(p, p.large[li]);
   if (p.carry) {
     a.sample_n = seg_sample_n(a.n);
     a.rs_out = p.carry + p.carry_off[li];
@@ -2143,8 +2147,9 @@ __device__ __forceinline__ StepArgs seg_large_args(const SegPlan& p, int li) {
 // block_select_comp over LDS, then every element written from LDS with independent coalesced
 // stores and the payload placed by one LDS atomic per wave (order within the segment is free: the
 // exchange and the decode are order-independent).  small_body's ordered one-round-per-1024
-// writes and serial loads made 116 ResNet-50 tensors a 46 us launch.
-template <bool HAS_RES, int MODE>
+// writes and serial loads made 116 ResNet-50 tensors a 46 us launch.  (bf16: an exact select that
+// writes r' = t - t itself, so kRKeepsT does not come into it.)
+template <bool HAS_RES, int MODE, typename E = float>
 __device__ void seg_small_body(const StepArgs& a, float* s_t, uint32_t* hist, uint32_t* s_w, uint32_t* s_res) {
   constexpr int kU = 8;
   const int tid = threadIdx.x;
@@ -2154,7 +2159,7 @@ __device__ void seg_small_body(const StepArgs& a, float* s_t, uint32_t* hist, ui
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
       const int64_t i = j0 + (int64_t)u * kSelBlock;
-      t[u] = compensate<HAS_RES>(a, i < n ? i : j0);   // clamped, unconditional
+      t[u] = compensate<HAS_RES, E>(a, i < n ? i : j0);   // clamped, unconditional
     }
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
@@ -2174,7 +2179,7 @@ __device__ void seg_small_body(const StepArgs& a, float* s_t, uint32_t* hist, ui
     const float v = st[i];
     const bool sel = comp_key(abs_key(v), (uint32_t)i) >= T;
     if constexpr (kWritesR<MODE>) a.r[i] = sel ? v - v : v;
-    if constexpr (kWritesOut<MODE>) a.out[i] = sel ? 0.f + v : 0.f;
+    if constexpr (kWritesOut<MODE>) st_elem(out_of<E>(a), i, sel ? 0.f + v : 0.f);
     const uint64_t m = __ballot(sel);
     uint32_t base = 0;
     if (m && lane_rank(m) == 0 && sel) base = atomicAdd(&s_res[0], (uint32_t)__popcll(m));
@@ -2187,7 +2192,7 @@ __device__ void seg_small_body(const StepArgs& a, float* s_t, uint32_t* hist, ui
   }
 }
 
-template <bool HAS_RES, int MODE>
+template <bool HAS_RES, int MODE, typename E = float>
 __global__ __launch_bounds__(kSelBlock) void seg_prep_kernel(SegPlan p) {
   // bracket: the fine sample histogram [kBracketBins]; small segment: t [kSmallN] + select histogram
   __shared__ uint32_t lds[kSmallN + 2048];
@@ -2196,11 +2201,11 @@ __global__ __launch_bounds__(kSelBlock) void seg_prep_kernel(SegPlan p) {
   static_assert(kBracketBins + kBracketBins / 32 <= kSmallN + 2048, "padded bracket histogram fits the shared block");
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b >= p.nL) {   // a small segment, selected and written completely by this workgroup
-    const StepArgs a = seg_step_args(p, p.small[b - p.nL]);
-    seg_small_body<HAS_RES, MODE>(a, reinterpret_cast<float*>(lds), lds + kSmallN, s_w, s_res);
+    const StepArgs a = seg_step_args<E>(p, p.small[b - p.nL]);
+    seg_small_body<HAS_RES, MODE, E>(a, reinterpret_cast<float*>(lds), lds + kSmallN, s_w, s_res);
     return;
   }
-  const StepArgs a = seg_large_args(p, b);
+  const StepArgs a = seg_large_args<E>(p, b);
   const TopkWs w = seg_ws(p, b, a.n, a.k);
   STAMP_IF(true, w.ctl, 13);
 #ifdef GRACE_STAMPS
@@ -2226,9 +2231,9 @@ __global__ __launch_bounds__(kSelBlock) void seg_prep_kernel(SegPlan p) {
       const float tp = a.rs_in[sc];
       const uint64_t Tp = *reinterpret_cast<const uint64_t*>(a.rs_in + carry_thr_off(S));
       const float rp = comp_key(abs_key(tp), (uint32_t)pos) >= Tp ? tp - tp : tp;
-      t[q] = a.beta * rp + a.gamma * a.g[pos];
+      t[q] = a.beta * rp + a.gamma * ld_elem(g_of<E>(a), pos);
     } else {
-      t[q] = compensate<HAS_RES>(a, pos);
+      t[q] = compensate<HAS_RES, E>(a, pos);
     }
   }
   if (a.rs_out) {
@@ -2256,13 +2261,13 @@ __global__ __launch_bounds__(kSelBlock) void seg_prep_kernel(SegPlan p) {
   STAMP_IF(true, w.ctl, 15);
 }
 
-template <bool HAS_RES, int MODE, bool VEC>
+template <bool HAS_RES, int MODE, bool VEC, typename E = float>
 __global__ __launch_bounds__(kMainBlock, 4) void seg_main_kernel(SegPlan p) {
   __shared__ MainShared sm;
   const int tid = threadIdx.x;
   const int li = p.chunk_li[blockIdx.x];
   const int s = p.large[li];
-  const StepArgs a = seg_step_args(p, s);
+  const StepArgs a = seg_step_args<E>(p, s);
   const TopkWs w = seg_ws(p, li, a.n, a.k);
   const int64_t chunk = (int64_t)blockIdx.x - p.chk_off[li];
 #ifdef GRACE_STAMPS
@@ -2276,10 +2281,12 @@ __global__ __launch_bounds__(kMainBlock, 4) void seg_main_kernel(SegPlan p) {
   uint32_t wfill;
   // (no beta = gamma = 1 instantiation here: next to the segment bookkeeping it pushed this kernel
   // to 128 VGPRs and 96 B of scratch per lane)
-  if (VEC && (p.seg_off[s] & 3) == 0 && (chunk + 1) * kChunkOf<HAS_RES, MODE> <= a.n) {
-    wfill = main_chunk<HAS_RES, MODE, VEC>(a, w, sm, lo, hi, sh, mid, chunk);
+  // (seg_off & 3: four elements of every stream per aligned access, 16 B of f32 or 8 B of bf16)
+  constexpr int NV = kVecOf<HAS_RES, MODE, E>;
+  if (VEC && (p.seg_off[s] & 3) == 0 && (chunk + 1) * kChunkOf<HAS_RES, MODE, E> <= a.n) {
+    wfill = main_chunk<HAS_RES, MODE, VEC, false, false, false, NV, E>(a, w, sm, lo, hi, sh, mid, chunk);
   } else {
-    wfill = main_chunk<HAS_RES, MODE, false>(a, w, sm, lo, hi, sh, mid, chunk);
+    wfill = main_chunk<HAS_RES, MODE, false, false, false, false, NV, E>(a, w, sm, lo, hi, sh, mid, chunk);
   }
   flush_staged(a, w, sm, lo, hi, sh, mid, wfill);
   __syncthreads();
@@ -2297,32 +2304,95 @@ __global__ __launch_bounds__(kMainBlock, 4) void seg_main_kernel(SegPlan p) {
 // the engine's finalize per large segment, with the segment's fin_off[li + 1] - fin_off[li]
 // workgroups (sized on the host for ~2 k_i candidates, one round of kSelBlock * kFinPer each) and
 // its own last arriver; no parallel exact fallback (its grid barrier would span segments): a missed
-// bracket falls back to the last workgroup's exact select over the segment
-template <int MODE>
+// bracket falls back to the last workgroup's exact select over the segment.  bf16 with a dense output
+// is the kRKeepsT form: t is still in r after the main pass, the finalize zeroes the k_i selected
+// positions there, and the fallback reads t from r -- never from g, which `out` may alias.
+template <int MODE, typename E = float>
 __global__ __launch_bounds__(kSelBlock) void seg_fin_kernel(SegPlan p) {
   __shared__ FinShared<kSelBlock> fs;
   const int li = p.fin_li[blockIdx.x];
   const int fi = (int)((int64_t)blockIdx.x - p.fin_off[li]);
   const int fcnt = (int)(p.fin_off[li + 1] - p.fin_off[li]);
-  const StepArgs a = seg_large_args(p, li);
+  const StepArgs a = seg_large_args<E>(p, li);
   const TopkWs w = seg_ws(p, li, a.n, a.k);
   STAMP_IF(fi == 0, w.ctl, 8);
-  finalize_run<MODE, kSelBlock, false>(a, w, fi, fcnt, fs, false);
+  finalize_run<MODE, kSelBlock, false, E>(a, w, fi, fcnt, fs, false);
 }
 
-template <bool HAS_RES, int MODE>
+template <bool HAS_RES, int MODE, typename E = float>
 static grace_status_t run_segmented(const SegPlan& p, int64_t nchunks, int64_t nfin, bool vec, hipStream_t s) {
-  seg_prep_kernel<HAS_RES, MODE><<<(unsigned)(p.nL + p.nS), kSelBlock, 0, s>>>(p);
+  seg_prep_kernel<HAS_RES, MODE, E><<<(unsigned)(p.nL + p.nS), kSelBlock, 0, s>>>(p);
   GRACE_CHECK_LAUNCH("grace_topk_segmented_step");
   if (p.nL == 0) return GRACE_OK;
   if (vec)
-    launch_timed(seg_main_kernel<HAS_RES, MODE, true>, dim3((unsigned)nchunks), dim3(kMainBlock), s, p);
+    launch_timed(seg_main_kernel<HAS_RES, MODE, true, E>, dim3((unsigned)nchunks), dim3(kMainBlock), s, p);
   else
-    launch_timed(seg_main_kernel<HAS_RES, MODE, false>, dim3((unsigned)nchunks), dim3(kMainBlock), s, p);
+    launch_timed(seg_main_kernel<HAS_RES, MODE, false, E>, dim3((unsigned)nchunks), dim3(kMainBlock), s, p);
   GRACE_CHECK_LAUNCH("grace_topk_segmented_step");
-  seg_fin_kernel<MODE><<<(unsigned)nfin, kSelBlock, 0, s>>>(p);
+  seg_fin_kernel<MODE, E><<<(unsigned)nfin, kSelBlock, 0, s>>>(p);
   GRACE_CHECK_LAUNCH("grace_topk_segmented_step");
   return GRACE_OK;
+}
+
+// grace_topk_segmented_step[_bf16]: g / out hold E (bf16 in the float-typed pointers: as_g / as_out)
+template <typename E>
+static grace_status_t segmented_step(const float* g, float* residual, int32_t has_residual, float beta, float gamma,
+                                     const int64_t* seg_off, const int64_t* k_off, const int32_t* large,
+                                     int32_t n_large, const int32_t* small, int32_t n_small, const int64_t* chk_off,
+                                     const int32_t* chunk_li, int64_t nchunks, const int64_t* ws_off,
+                                     const int64_t* fin_off, const int32_t* fin_li, int64_t nfin, int64_t n_total,
+                                     float* vals, int32_t* idx, float* out, float* carry, const int64_t* carry_off,
+                                     int32_t carry_valid, void* ws, size_t ws_bytes, int64_t ws_need, void* stream) {
+  GRACE_REQUIRE(g && residual && seg_off && k_off && vals && idx && n_large >= 0 && n_small >= 0 &&
+                    n_large + n_small >= 1 && n_total >= 1 && n_total < ((int64_t)1 << 31) &&
+                    (n_large == 0 || (large && chk_off && chunk_li && ws_off && fin_off && fin_li && ws &&
+                                      nchunks >= 1 && nfin >= n_large)) &&
+                    (n_small == 0 || small),
+                kIsBf16<E> ? "grace_topk_segmented_step_bf16: bad arguments"
+                           : "grace_topk_segmented_step: bad arguments");
+  SegPlan p{};
+  p.g = g;
+  p.r = residual;
+  p.out = out;
+  p.vals = vals;
+  p.idx = idx;
+  p.beta = beta;
+  p.gamma = gamma;
+  p.seg_off = seg_off;
+  p.k_off = k_off;
+  p.large = large;
+  p.small = small;
+  p.chk_off = chk_off;
+  p.chunk_li = chunk_li;
+  p.ws_off = ws_off;
+  p.fin_off = fin_off;
+  p.fin_li = fin_li;
+  p.ws = reinterpret_cast<char*>(ws);
+  p.nL = n_large;
+  p.nS = n_small;
+  GRACE_REQUIRE(!carry || carry_off, kIsBf16<E> ? "grace_topk_segmented_step_bf16: carry without carry_off"
+                                                : "grace_topk_segmented_step: carry without carry_off");
+  // written by every step (a first step without a residual records t = g), read only with a
+  // residual whose previous step wrote it
+  p.carry = carry;
+  p.carry_off = carry_off;
+  p.carry_valid = carry && has_residual && carry_valid ? 1 : 0;
+  GRACE_REQUIRE(n_large == 0 || (ws_need > 0 && ws_bytes >= (size_t)ws_need),
+                kIsBf16<E>
+                    ? "grace_topk_segmented_step_bf16: workspace smaller than grace_topk_segmented_workspace_bytes"
+                    : "grace_topk_segmented_step: workspace smaller than grace_topk_segmented_workspace_bytes");
+  // four elements of every stream per aligned access: 16 B of f32, 8 B of bf16 (r is always f32)
+  StepArgs al{};
+  al.g = g;
+  al.r = residual;
+  al.out = out;
+  const bool vec = quad_aligned<E>(al);
+  hipStream_t s = as_stream(stream);
+  if (has_residual)
+    return out ? run_segmented<true, kDenseFused, E>(p, nchunks, nfin, vec, s)
+               : run_segmented<true, kDenseRes, E>(p, nchunks, nfin, vec, s);
+  return out ? run_segmented<false, kDenseFused, E>(p, nchunks, nfin, vec, s)
+             : run_segmented<false, kDenseRes, E>(p, nchunks, nfin, vec, s);
 }
 
 }  // namespace grace
@@ -2776,6 +2846,11 @@ int64_t grace_topk_segmented_chunk(int32_t has_residual, int32_t dense_out) {
   return dense_out ? kChunkOf<false, kDenseFused> : kChunkOf<false, kDenseRes>;
 }
 
+int64_t grace_topk_segmented_chunk_bf16(int32_t has_residual, int32_t dense_out) {
+  if (has_residual) return dense_out ? kChunkOf<true, kDenseFused, uint16_t> : kChunkOf<true, kDenseRes, uint16_t>;
+  return dense_out ? kChunkOf<false, kDenseFused, uint16_t> : kChunkOf<false, kDenseRes, uint16_t>;
+}
+
 int64_t grace_topk_segmented_seg_ws_bytes(int64_t n, int64_t k) { return seg_ws_bytes_one(n, k); }
 
 // f32 words of a large segment's carry: t at its sample positions + the u64 threshold
@@ -2810,48 +2885,25 @@ grace_status_t grace_topk_segmented_step(const float* g, float* residual, int32_
                                          int32_t* idx, float* out, float* carry, const int64_t* carry_off,
                                          int32_t carry_valid, void* ws, size_t ws_bytes, int64_t ws_need,
                                          void* stream) {
-  GRACE_REQUIRE(g && residual && seg_off && k_off && vals && idx && n_large >= 0 && n_small >= 0 &&
-                    n_large + n_small >= 1 && n_total >= 1 && n_total < ((int64_t)1 << 31) &&
-                    (n_large == 0 || (large && chk_off && chunk_li && ws_off && fin_off && fin_li && ws &&
-                                      nchunks >= 1 && nfin >= n_large)) &&
-                    (n_small == 0 || small),
-                "grace_topk_segmented_step: bad arguments");
-  SegPlan p{};
-  p.g = g;
-  p.r = residual;
-  p.out = out;
-  p.vals = vals;
-  p.idx = idx;
-  p.beta = beta;
-  p.gamma = gamma;
-  p.seg_off = seg_off;
-  p.k_off = k_off;
-  p.large = large;
-  p.small = small;
-  p.chk_off = chk_off;
-  p.chunk_li = chunk_li;
-  p.ws_off = ws_off;
-  p.fin_off = fin_off;
-  p.fin_li = fin_li;
-  p.ws = reinterpret_cast<char*>(ws);
-  p.nL = n_large;
-  p.nS = n_small;
-  GRACE_REQUIRE(!carry || carry_off, "grace_topk_segmented_step: carry without carry_off");
-  // written by every step (a first step without a residual records t = g), read only with a
-  // residual whose previous step wrote it
-  p.carry = carry;
-  p.carry_off = carry_off;
-  p.carry_valid = carry && has_residual && carry_valid ? 1 : 0;
-  GRACE_REQUIRE(n_large == 0 || (ws_need > 0 && ws_bytes >= (size_t)ws_need),
-                "grace_topk_segmented_step: workspace smaller than grace_topk_segmented_workspace_bytes");
-  const bool vec = ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(residual) |
-                     reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
-  hipStream_t s = as_stream(stream);
-  if (has_residual)
-    return out ? run_segmented<true, kDenseFused>(p, nchunks, nfin, vec, s)
-               : run_segmented<true, kDenseRes>(p, nchunks, nfin, vec, s);
-  return out ? run_segmented<false, kDenseFused>(p, nchunks, nfin, vec, s)
-             : run_segmented<false, kDenseRes>(p, nchunks, nfin, vec, s);
+  return segmented_step<float>(g, residual, has_residual, beta, gamma, seg_off, k_off, large, n_large, small, n_small,
+                               chk_off, chunk_li, nchunks, ws_off, fin_off, fin_li, nfin, n_total, vals, idx, out,
+                               carry, carry_off, carry_valid, ws, ws_bytes, ws_need, stream);
+}
+
+// bf16 gradients and dense result (f32 residual, payload and carry): per tensor what
+// grace_topk_residual_step_bf16 computes; `out` may be `g` itself
+grace_status_t grace_topk_segmented_step_bf16(const uint16_t* g, float* residual, int32_t has_residual, float beta,
+                                              float gamma, const int64_t* seg_off, const int64_t* k_off,
+                                              const int32_t* large, int32_t n_large, const int32_t* small,
+                                              int32_t n_small, const int64_t* chk_off, const int32_t* chunk_li,
+                                              int64_t nchunks, const int64_t* ws_off, const int64_t* fin_off,
+                                              const int32_t* fin_li, int64_t nfin, int64_t n_total, float* vals,
+                                              int32_t* idx, uint16_t* out, float* carry, const int64_t* carry_off,
+                                              int32_t carry_valid, void* ws, size_t ws_bytes, int64_t ws_need,
+                                              void* stream) {
+  return segmented_step<uint16_t>(as_g(g), residual, has_residual, beta, gamma, seg_off, k_off, large, n_large, small,
+                                  n_small, chk_off, chunk_li, nchunks, ws_off, fin_off, fin_li, nfin, n_total, vals,
+                                  idx, as_out(out), carry, carry_off, carry_valid, ws, ws_bytes, ws_need, stream);
 }
 
 }  // extern "C"

@@ -22,7 +22,9 @@ def step_parameters(model, grc):
 
 
 class GradBucket:
-    """One flat f32 buffer holding every parameter's gradient (parameters' .grad become views).
+    """One flat buffer holding every parameter's gradient (parameters' .grad become views), in the
+    parameters' dtype: float32, or bfloat16 for a bf16 model (step_segmented takes either; all
+    trainable parameters must share one).
     Autograd accumulates into the existing .grad views in place, so a backward pass writes straight
     into ``flat``; clear it with ``zero_()`` (not ``optimizer.zero_grad()``, whose default
     set_to_none=True would detach the views)."""
@@ -31,7 +33,11 @@ class GradBucket:
         params = [p for p in model.parameters() if p.requires_grad]
         total = sum(p.numel() for p in params)
         dev = params[0].device
-        self.flat = torch.zeros(total, dtype=torch.float32, device=dev)
+        dtypes = {p.dtype for p in params}
+        if len(dtypes) != 1 or not dtypes <= {torch.float32, torch.bfloat16}:
+            raise TypeError("grace_amd: GradBucket needs all trainable parameters in one dtype, float32 or "
+                            f"bfloat16; got {sorted(str(d) for d in dtypes)}")
+        self.flat = torch.zeros(total, dtype=params[0].dtype, device=dev)
         off = 0
         for p in params:
             n = p.numel()

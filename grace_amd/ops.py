@@ -792,13 +792,20 @@ def sort_payload(buf, k, n):
     return out
 
 
-def sparse_aggregate_sorted(gathered, k, world, n, divisor, out_dtype=F32):
+def sparse_aggregate_sorted(gathered, k, world, n, divisor, out_dtype=F32, out=None):
     """Rank-ordered aggregate of W chunk-grouped payloads (rank-major, stride sorted_payload_len).
     out_dtype=torch.bfloat16: the same f32 sum and division rounded once to bf16 in the decode's
-    epilogue (grace_sparse_aggregate_sorted_bf16)."""
+    epilogue (grace_sparse_aggregate_sorted_bf16).  out: the caller's contiguous buffer of n
+    out_dtype elements on the payloads' device (the decode writes every element of it: each
+    8192-element chunk leaves as one dense tile, zeros included, so no pre-fill)."""
     if out_dtype != F32 and out_dtype != BF16:
         raise TypeError(f"grace_amd: sparse_aggregate_sorted writes float32 or bfloat16, got {out_dtype}")
-    out = torch.empty(n, dtype=out_dtype, device=gathered.device)
+    if out is None:
+        out = torch.empty(n, dtype=out_dtype, device=gathered.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == out_dtype and out.numel() == n and out.is_contiguous()
+              and out.device == gathered.device):
+        raise ValueError(f"grace_amd: sparse_aggregate_sorted: out must be a contiguous {out_dtype} tensor of "
+                         f"{n} elements on {gathered.device}")
     stride = sorted_payload_len(k, n)
     _lib.call("grace_sparse_aggregate_sorted_bf16" if out_dtype == BF16 else "grace_sparse_aggregate_sorted",
               _p(gathered), _p(gathered[k:]), _p(gathered[k + _off_words(k):]),

@@ -435,9 +435,17 @@ grace_status_t grace_fp16_decompress_aggregate(const void* half_in, int64_t stri
  * carry (may be NULL; has_residual only): f32, grace_topk_segmented_carry_len(n) words per large
  * segment at carry_off[n_large] -- the segment's t at its sample positions and its selection
  * threshold, written by the step; carry_valid: they are the previous step's for this residual
- * (the next prep then reads g alone at the sample positions). */
+ * (the next prep then reads g alone at the sample positions).
+ * grace_topk_segmented_step_bf16: the same step on bfloat16 gradients (g, and the dense result out,
+ * as uint16_t bit patterns); the residual, the payload and the carry stay f32.  Per tensor it is
+ * grace_topk_residual_step_bf16: every result is what grace_topk_segmented_step computes for the
+ * gradient widened to f32, out rounded once to nearest even; out may alias g.  Its main-pass chunks
+ * are grace_topk_segmented_chunk_bf16(has_residual, out != NULL) elements (build chk_off / chunk_li
+ * with that); every other table and query is shared with the f32 step.  The vector paths want g and
+ * out 8-byte aligned and residual 16-byte aligned; anything else takes the guarded path. */
 int32_t grace_topk_segmented_small_max(void);
 int64_t grace_topk_segmented_chunk(int32_t has_residual, int32_t dense_out);
+int64_t grace_topk_segmented_chunk_bf16(int32_t has_residual, int32_t dense_out);
 int64_t grace_topk_segmented_seg_ws_bytes(int64_t n, int64_t k);
 int32_t grace_topk_segmented_fin_blocks(int64_t n, int64_t k);
 /* The workspace a segment table needs (host arrays sizes[count], ks[count]: the LARGE segments,
@@ -454,6 +462,15 @@ grace_status_t grace_topk_segmented_step(const float* g, float* residual, int32_
                                          int32_t* idx, float* out, float* carry, const int64_t* carry_off,
                                          int32_t carry_valid, void* ws, size_t ws_bytes, int64_t ws_need,
                                          void* stream);
+grace_status_t grace_topk_segmented_step_bf16(const uint16_t* g, float* residual, int32_t has_residual, float beta,
+                                              float gamma, const int64_t* seg_off, const int64_t* k_off,
+                                              const int32_t* large, int32_t n_large, const int32_t* small,
+                                              int32_t n_small, const int64_t* chk_off, const int32_t* chunk_li,
+                                              int64_t nchunks, const int64_t* ws_off, const int64_t* fin_off,
+                                              const int32_t* fin_li, int64_t nfin, int64_t n_total, float* vals,
+                                              int32_t* idx, uint16_t* out, float* carry, const int64_t* carry_off,
+                                              int32_t carry_valid, void* ws, size_t ws_bytes, int64_t ws_need,
+                                              void* stream);
 int64_t grace_topk_segmented_carry_len(int64_t n);
 
 /* ---------------------------------------------------------------------- random-k / threshold */

@@ -41,6 +41,7 @@ SIGNATURES = {
     "grace_sub": (ST, [P, P, P, I64, P]),
     "grace_div_scalar": (ST, [P, F32, P, I64, P]),
     "grace_fill": (ST, [P, F32, I64, P]),
+    "grace_fill_bf16": (ST, [P, ctypes.c_uint16, I64, P]),
     "grace_hbm_probe_elems": (I64, [I64, I32]),
     "grace_hbm_probe": (ST, [P, P, P, I64, I32, P]),
     "grace_accumulate": (ST, [P, P, I64, I32, P]),
@@ -83,6 +84,8 @@ SIGNATURES = {
     "grace_shard_select_workspace_bytes": (SZ, [I32, I64]),
     "grace_shard_select": (ST, [P, I32, I32, I64, P, I64, P, P, I64, I64, P, P, P, SZ, P, P]),
     "grace_shard_clear": (ST, [P, I64, I64, P, I64, P]),
+    "grace_shard_select_bf16": (ST, [P, I32, I32, I64, P, I64, P, P, I64, I64, P, P, P, SZ, P, P]),
+    "grace_shard_clear_bf16": (ST, [P, I64, I64, P, I64, P]),
     "grace_dgc_workspace_bytes": (SZ, [I64]),
     "grace_dgc_sample": (ST, [P, I64, P, U64, I64, P, P]),
     "grace_dgc_threshold": (ST, [P, I64, P, I64, ctypes.c_double, P, P]),

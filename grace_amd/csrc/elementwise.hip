@@ -413,6 +413,34 @@ static int64_t probe_chunk(int variant) {
   return variant == 0 ? 8192 : variant == 1 ? 12288 : variant == 2 ? 16384 : variant == 6 ? 8192 : variant == 7 ? 16384 : 0;
 }
 
+// bf16 fill (grace_fill_bf16): `bits` into n 2-byte elements from any 2-byte aligned address.  The
+// body is whole 16-B lines written with non-temporal 16-B stores, one 16 KiB tile (1024 lines, four
+// per lane) per workgroup and round; the up to 7 elements before the first 16-B boundary and the up
+// to 7 after the last whole line are element stores of workgroup 0.
+typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+constexpr int kFillTile = 1024;   // 16-B lines per workgroup and round
+__global__ __launch_bounds__(256) void fill_bf16_kernel(uint16_t* __restrict__ x, uint16_t bits, int64_t n) {
+  int64_t head = (int64_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(x) & 15u)) & 15u) >> 1;
+  head = head < n ? head : n;
+  const int64_t nq = (n - head) >> 3;   // whole lines of 8 elements
+  u32x4v* body = reinterpret_cast<u32x4v*>(x + head);
+  const uint32_t w = (uint32_t)bits | ((uint32_t)bits << 16);
+  const u32x4v q = {w, w, w, w};
+  for (int64_t t0 = (int64_t)blockIdx.x * kFillTile; t0 < nq; t0 += (int64_t)gridDim.x * kFillTile) {
+#pragma unroll
+    for (int u = 0; u < kFillTile / 256; ++u) {
+      const int64_t i = t0 + u * 256 + threadIdx.x;
+      if (i < nq) __builtin_nontemporal_store(q, body + i);
+    }
+  }
+  if (blockIdx.x == 0) {
+    const int64_t t = threadIdx.x;
+    if (t < head) x[t] = bits;
+    const int64_t i = head + (nq << 3) + t;   // the tail: fewer than 8 elements
+    if (i < n) x[i] = bits;
+  }
+}
+
 }  // namespace grace
 
 using namespace grace;
@@ -485,6 +513,17 @@ grace_status_t grace_fill(float* x, float value, int64_t n, void* stream) {
   const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(x), (int)__builtin_bit_cast(uint32_t, value),
                                          (size_t)n, as_stream(stream));
   if (e != hipSuccess) { set_error("grace_fill", e); return GRACE_ERR_HIP; }
+  return GRACE_OK;
+}
+
+// the same for 2-byte elements (the zero-fill of a bfloat16 dense output): x 2-byte aligned, any n
+grace_status_t grace_fill_bf16(uint16_t* x, uint16_t bits, int64_t n, void* stream) {
+  GRACE_REQUIRE(n >= 0 && x && (reinterpret_cast<uintptr_t>(x) & 1u) == 0, "grace_fill_bf16: bad arguments");
+  if (n == 0) return GRACE_OK;
+  int64_t g = ((n >> 3) + kFillTile - 1) / kFillTile;
+  g = g < 1 ? 1 : (g > 65536 ? 65536 : g);
+  fill_bf16_kernel<<<(unsigned)g, 256, 0, as_stream(stream)>>>(x, bits, n);
+  GRACE_CHECK_LAUNCH("grace_fill_bf16");
   return GRACE_OK;
 }
 

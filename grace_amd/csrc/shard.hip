@@ -91,6 +91,7 @@ struct ShArgs {
   int64_t k;
   float* r;             // this rank's residual shard
   float* out;           // dense output, zero-filled, global range [out_base, out_base + out_len)
+                        // (bf16: the uint16_t buffer in the float-typed field, out_of<O>)
   int64_t out_base, out_len;
   int32_t* pay_idx;     // this rank's record entries: global index if selected, -1 otherwise
   int32_t* sel_gi;      // optional [world * cap]: every entry's global index if selected, else -1
@@ -121,14 +122,31 @@ __device__ __forceinline__ void split_entry(uint32_t e, uint32_t cap, uint32_t& 
 __device__ __forceinline__ int coarse_bin(uint32_t key) { return (int)(key >> 20); }
 __device__ __forceinline__ int sub_bin(uint32_t key) { return (int)((key >> 9) & (kShBins - 1)); }
 
+// The select and the clear are instantiated per element type O of the dense output: float, or
+// uint16_t for bfloat16 bits (grace_shard_select_bf16 / grace_shard_clear_bf16).  ShArgs declares
+// `out` as a float pointer; the uint16_t instantiations read it through out_of<O> (topk.hip's
+// convention for StepArgs).  Only the store of a selected value differs: 0 + v rounded once to
+// nearest even in integer arithmetic (common.h f32_to_bf16, not the hardware convert: DESIGN.md §9)
+// and written as a plain 2-byte store -- two selected positions may share a dword, their addresses
+// are distinct.  The records, the residual, pay_idx, sel_gi, the histograms and the lists are f32 /
+// int for either type.
+template <typename O> constexpr bool kShBf16 = sizeof(O) == 2;
+template <typename O>
+__device__ __forceinline__ O* out_of(const ShArgs& a) { return reinterpret_cast<O*>(a.out); }
+
 // the decision for one entry: dense output, for this rank's entries pay_idx and the residual, and
 // the entry's selection record
+template <typename O>
 __device__ __forceinline__ void shard_take(const ShArgs& a, bool sel, uint32_t w, uint32_t j, int32_t li, float v,
                                            int64_t gbase) {
   const int64_t gi = gbase + li;
   if (sel) {
     const int64_t o = gi - a.out_base;
-    if (o >= 0 && o < a.out_len) a.out[o] = 0.f + v;
+    if constexpr (kShBf16<O>) {
+      if (o >= 0 && o < a.out_len) out_of<O>(a)[o] = f32_to_bf16(0.f + v);
+    } else {
+      if (o >= 0 && o < a.out_len) a.out[o] = 0.f + v;
+    }
   }
   if ((int32_t)w == a.rank) {
     a.pay_idx[j] = sel ? (int32_t)gi : -1;
@@ -229,6 +247,7 @@ __device__ __forceinline__ void coarse_round(uint32_t e0, uint32_t N, const int3
 // the coarse cut over one round = one list block (its entries loaded by the caller): above C1
 // selected, below rejected; the C1 entries counted into the LDS sub-bin histogram hl and compacted
 // into the same block of the C1 list, their count in bcnt -- no global reservation
+template <typename O>
 __device__ __forceinline__ void apply_round(const ShArgs& a, uint32_t r0, uint32_t N, int c1,
                                             const int32_t (&li)[kShPer], const float (&v)[kShPer],
                                             uint32_t* hl, const int64_t* s_base, uint32_t* s_cnt) {
@@ -250,7 +269,7 @@ __device__ __forceinline__ void apply_round(const ShArgs& a, uint32_t r0, uint32
         const int cb = coarse_bin(key);
         inb = cb == c1;
         if (inb) atomicAdd(&hl[sub_bin(key)], 1u);
-        else shard_take(a, cb > c1, w, j, li[u], v[u], s_base[w]);
+        else shard_take<O>(a, cb > c1, w, j, li[u], v[u], s_base[w]);
       }
     }
     // C1 entries placed by one LDS atomic per wave
@@ -287,6 +306,7 @@ __device__ __forceinline__ void apply_round(const ShArgs& a, uint32_t r0, uint32
 // the sub-bin cut over one block of the C1 list (its count and entries loaded by the caller): the
 // entries outside the cut sub-bin b2 decided; the b2 entries appended, whole, to the cut list
 // (write-through for the last arriver)
+template <typename O>
 __device__ __forceinline__ void bnd_round(const ShArgs& a, uint32_t cnt_b, const uint4 (&q4)[kShPer], int b2,
                                           const int64_t* s_base, uint32_t* s_cnt, uint32_t* s_gbase) {
   const int t = threadIdx.x;
@@ -301,7 +321,7 @@ __device__ __forceinline__ void bnd_round(const ShArgs& a, uint32_t cnt_b, const
       const float v = u2f(q4[u].z);
       const int sb = sub_bin(abs_key(v));
       in2 = sb == b2;
-      if (!in2) shard_take(a, sb > b2, w, j, (int32_t)((int64_t)q4[u].y - s_base[w]), v, s_base[w]);
+      if (!in2) shard_take<O>(a, sb > b2, w, j, (int32_t)((int64_t)q4[u].y - s_base[w]), v, s_base[w]);
     }
     const uint64_t m = __ballot(in2);
     off[u] = ~0u;
@@ -326,6 +346,7 @@ __device__ __forceinline__ void bnd_round(const ShArgs& a, uint32_t cnt_b, const
 
 // the last arriver: the cut sub-bin's entries ranked exactly by the composite (key, global index),
 // the need2 highest selected; then the sub-bin histogram copies re-zeroed
+template <typename O>
 __device__ __forceinline__ void rank_cut(const ShArgs& a, uint32_t need2, const int64_t* s_base, uint64_t* s_comp,
                                          uint32_t* hl, uint32_t* s_w, uint32_t* s_res) {
   const int t = threadIdx.x;
@@ -363,7 +384,7 @@ __device__ __forceinline__ void rank_cut(const ShArgs& a, uint32_t need2, const 
       int32_t l;
       float x;
       entry(q, w, j, l, x);
-      shard_take(a, rk < need2, w, j, l, x, s_base[w]);
+      shard_take<O>(a, rk < need2, w, j, l, x, s_base[w]);
     }
   } else {
     // massive ties (more than kShPairCap entries share key bits 31..9): exact radix select over
@@ -381,7 +402,7 @@ __device__ __forceinline__ void rank_cut(const ShArgs& a, uint32_t need2, const 
       int32_t l;
       float x;
       entry(q, w, j, l, x);
-      shard_take(a, comp_key(abs_key(x), q.y) >= T, w, j, l, x, s_base[w]);
+      shard_take<O>(a, comp_key(abs_key(x), q.y) >= T, w, j, l, x, s_base[w]);
     }
   }
   SH_STAMP(true, a.ctl, 14);
@@ -427,6 +448,7 @@ __global__ __launch_bounds__(kShBlock) void shard_coarse_kernel(ShArgs a) {
 }
 
 // 3b. the coarse cut: above C1 selected, below rejected; the C1 entries listed and sub-binned
+template <typename O>
 __global__ __launch_bounds__(kShBlock) void shard_apply_kernel(ShArgs a) {
   __shared__ int64_t s_base[kShMaxWorld];
   __shared__ uint32_t hl[kShBins];
@@ -456,7 +478,7 @@ __global__ __launch_bounds__(kShBlock) void shard_apply_kernel(ShArgs a) {
   // uniform rounds (the workgroup barriers inside): every thread runs every round
   for (uint32_t r0 = blockIdx.x * kShListBlock; r0 < N; r0 += gridDim.x * kShListBlock) {
     if (r0 != blockIdx.x * kShListBlock) load_entries(a, r0 + t, N, li, v);
-    apply_round(a, r0, N, c1, li, v, hl, s_base, &s_cnt);
+    apply_round<O>(a, r0, N, c1, li, v, hl, s_base, &s_cnt);
   }
   SH_STAMP(blockIdx.x == 0, a.ctl, 9);
   flush_copy(a.hist2, hl);
@@ -464,6 +486,7 @@ __global__ __launch_bounds__(kShBlock) void shard_apply_kernel(ShArgs a) {
 }
 
 // 3c. the sub-bin cut over the C1 list in parallel; the last arriver ranks the cut sub-bin
+template <typename O>
 __global__ __launch_bounds__(kShBlock) void shard_bnd_kernel(ShArgs a) {
   static_assert(kShPairCap <= kShBlock, "the pairwise ranking holds one cut entry per thread");
   __shared__ int64_t s_base[kShMaxWorld];
@@ -500,7 +523,7 @@ __global__ __launch_bounds__(kShBlock) void shard_bnd_kernel(ShArgs a) {
 #pragma unroll
       for (int u = 0; u < kShPer; ++u) q4[u] = a.bnd[blk * kShListBlock + t + u * kShBlock];   // in flight with cnt_b
     }
-    bnd_round(a, cnt_b, q4, b2, s_base, &s_cnt, &s_gbase);
+    bnd_round<O>(a, cnt_b, q4, b2, s_base, &s_cnt, &s_gbase);
   }
   // the coarse histogram's copies were last read by shard_apply: re-zeroed here by every workgroup
   // (the sub-bin copies, read above, by the last arriver)
@@ -513,14 +536,15 @@ __global__ __launch_bounds__(kShBlock) void shard_bnd_kernel(ShArgs a) {
   __syncthreads();
   if (!s_last) return;
   SH_STAMP(true, a.ctl, 6);
-  rank_cut(a, need2, s_base, s_comp, hl, s_w, s_res);
+  rank_cut<O>(a, need2, s_base, s_comp, hl, s_w, s_res);
   if (t == 0) a.ctl->ticket = 0u;
   SH_STAMP(true, a.ctl, 7);
 }
 
 // recycled output: zero the previous step's selected positions (its sel_gi list), 8 index loads in
 // flight per thread
-__global__ __launch_bounds__(256) void shard_clear_kernel(float* __restrict__ out, int64_t out_base, int64_t out_len,
+template <typename O>
+__global__ __launch_bounds__(256) void shard_clear_kernel(O* __restrict__ out, int64_t out_base, int64_t out_len,
                                                          const int32_t* __restrict__ sel_gi, int64_t count) {
   constexpr int kU = 8;
   for (int64_t j0 = (int64_t)blockIdx.x * 256 * kU + threadIdx.x; j0 < count; j0 += (int64_t)gridDim.x * 256 * kU) {
@@ -533,7 +557,7 @@ __global__ __launch_bounds__(256) void shard_clear_kernel(float* __restrict__ ou
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
       const int64_t o = (int64_t)gi[u] - out_base;
-      if (j0 + (int64_t)u * 256 < count && gi[u] >= 0 && o >= 0 && o < out_len) out[o] = 0.f;
+      if (j0 + (int64_t)u * 256 < count && gi[u] >= 0 && o >= 0 && o < out_len) out[o] = O(0);
     }
   }
 }
@@ -549,36 +573,30 @@ static size_t sh_ws_bytes(int64_t world, int64_t cap) {
   return 256 + 2 * sizeof(uint32_t) * kShGroups * kShBins + 2 * sh_list_bytes(world, cap) + sh_bcnt_bytes(world, cap);
 }
 
-}  // namespace grace
 
-using namespace grace;
-
-extern "C" {
-
-size_t grace_shard_record_words(int64_t cap) { return (size_t)(kShHdr + 2 * cap); }
-
-size_t grace_shard_select_workspace_bytes(int32_t world, int64_t cap) { return sh_ws_bytes(world, cap); }
-
-grace_status_t grace_shard_clear(float* out, int64_t out_base, int64_t out_len, const int32_t* sel_gi, int64_t count,
-                                 void* stream) {
-  GRACE_REQUIRE(out && sel_gi && out_base >= 0 && out_len >= 0 && count >= 0, "grace_shard_clear: bad arguments");
+// O: float, or uint16_t for a bf16 output; `name` is the entry point's own (its errors carry it)
+template <typename O>
+static grace_status_t shard_clear(const char* name, const char* bad, O* out, int64_t out_base, int64_t out_len,
+                                  const int32_t* sel_gi, int64_t count, void* stream) {
+  GRACE_REQUIRE(out && sel_gi && out_base >= 0 && out_len >= 0 && count >= 0, bad);
   if (count == 0) return GRACE_OK;
   int64_t g = (count + 256 * 8 - 1) / (256 * 8);
   g = g > 1024 ? 1024 : g;
-  shard_clear_kernel<<<(unsigned)g, 256, 0, as_stream(stream)>>>(out, out_base, out_len, sel_gi, count);
-  GRACE_CHECK_LAUNCH("grace_shard_clear");
+  shard_clear_kernel<O><<<(unsigned)g, 256, 0, as_stream(stream)>>>(out, out_base, out_len, sel_gi, count);
+  GRACE_CHECK_LAUNCH(name);
   return GRACE_OK;
 }
 
-grace_status_t grace_shard_select(const int32_t* recs, int32_t world, int32_t rank, int64_t cap, const int64_t* tab,
-                                  int64_t k, float* residual, float* out, int64_t out_base, int64_t out_len,
-                                  int32_t* pay_idx, int32_t* sel_gi, void* ws, size_t ws_bytes, int32_t* status_host,
-                                  void* stream) {
+template <typename O>
+static grace_status_t shard_select(const char* name, const char* bad, const char* small, const int32_t* recs,
+                                   int32_t world, int32_t rank, int64_t cap, const int64_t* tab, int64_t k,
+                                   float* residual, O* out, int64_t out_base, int64_t out_len, int32_t* pay_idx,
+                                   int32_t* sel_gi, void* ws, size_t ws_bytes, int32_t* status_host, void* stream) {
   GRACE_REQUIRE(recs && tab && residual && out && pay_idx && ws && world >= 1 && world <= kShMaxWorld &&
                     rank >= 0 && rank < world && cap >= 1 && k >= 1 && out_base >= 0 && out_len >= 0 &&
                     (int64_t)world * cap < ((int64_t)1 << 31),
-                "grace_shard_select: bad arguments");
-  GRACE_REQUIRE(ws_bytes >= sh_ws_bytes(world, cap), "grace_shard_select: workspace too small");
+                bad);
+  GRACE_REQUIRE(ws_bytes >= sh_ws_bytes(world, cap), small);
   char* p = reinterpret_cast<char*>(ws);
   ShArgs a;
   a.recs = recs;
@@ -589,7 +607,7 @@ grace_status_t grace_shard_select(const int32_t* recs, int32_t world, int32_t ra
   a.tab = tab;
   a.k = k;
   a.r = residual;
-  a.out = out;
+  a.out = reinterpret_cast<float*>(out);
   a.out_base = out_base;
   a.out_len = out_len;
   a.pay_idx = pay_idx;
@@ -606,13 +624,55 @@ grace_status_t grace_shard_select(const int32_t* recs, int32_t world, int32_t ra
   const unsigned grid = (unsigned)(g < 1 ? 1 : (g > kShMaxGrid ? kShMaxGrid : g));
   hipStream_t s = as_stream(stream);
   shard_coarse_kernel<<<grid, kShBlock, 0, s>>>(a);
-  GRACE_CHECK_LAUNCH("grace_shard_select");
-  shard_apply_kernel<<<grid, kShBlock, 0, s>>>(a);
-  GRACE_CHECK_LAUNCH("grace_shard_select");
+  GRACE_CHECK_LAUNCH(name);
+  shard_apply_kernel<O><<<grid, kShBlock, 0, s>>>(a);
+  GRACE_CHECK_LAUNCH(name);
   // one workgroup per block of the C1 list (the apply's grid)
-  shard_bnd_kernel<<<grid, kShBlock, 0, s>>>(a);
-  GRACE_CHECK_LAUNCH("grace_shard_select");
+  shard_bnd_kernel<O><<<grid, kShBlock, 0, s>>>(a);
+  GRACE_CHECK_LAUNCH(name);
   return GRACE_OK;
+}
+
+}  // namespace grace
+
+using namespace grace;
+
+extern "C" {
+
+size_t grace_shard_record_words(int64_t cap) { return (size_t)(kShHdr + 2 * cap); }
+
+size_t grace_shard_select_workspace_bytes(int32_t world, int64_t cap) { return sh_ws_bytes(world, cap); }
+
+grace_status_t grace_shard_clear(float* out, int64_t out_base, int64_t out_len, const int32_t* sel_gi, int64_t count,
+                                 void* stream) {
+  return shard_clear<float>("grace_shard_clear", "grace_shard_clear: bad arguments", out, out_base, out_len, sel_gi,
+                            count, stream);
+}
+
+// the same on a bfloat16 output (out holds bf16 bits): a 2-byte zero per position
+grace_status_t grace_shard_clear_bf16(uint16_t* out, int64_t out_base, int64_t out_len, const int32_t* sel_gi,
+                                      int64_t count, void* stream) {
+  return shard_clear<uint16_t>("grace_shard_clear_bf16", "grace_shard_clear_bf16: bad arguments", out, out_base,
+                               out_len, sel_gi, count, stream);
+}
+
+grace_status_t grace_shard_select(const int32_t* recs, int32_t world, int32_t rank, int64_t cap, const int64_t* tab,
+                                  int64_t k, float* residual, float* out, int64_t out_base, int64_t out_len,
+                                  int32_t* pay_idx, int32_t* sel_gi, void* ws, size_t ws_bytes, int32_t* status_host,
+                                  void* stream) {
+  return shard_select<float>("grace_shard_select", "grace_shard_select: bad arguments",
+                             "grace_shard_select: workspace too small", recs, world, rank, cap, tab, k, residual, out,
+                             out_base, out_len, pay_idx, sel_gi, ws, ws_bytes, status_host, stream);
+}
+
+// the same select into a bfloat16 output (out holds bf16 bits): every selected value rounded once
+grace_status_t grace_shard_select_bf16(const int32_t* recs, int32_t world, int32_t rank, int64_t cap,
+                                       const int64_t* tab, int64_t k, float* residual, uint16_t* out, int64_t out_base,
+                                       int64_t out_len, int32_t* pay_idx, int32_t* sel_gi, void* ws, size_t ws_bytes,
+                                       int32_t* status_host, void* stream) {
+  return shard_select<uint16_t>("grace_shard_select_bf16", "grace_shard_select_bf16: bad arguments",
+                                "grace_shard_select_bf16: workspace too small", recs, world, rank, cap, tab, k,
+                                residual, out, out_base, out_len, pay_idx, sel_gi, ws, ws_bytes, status_host, stream);
 }
 
 }  // extern "C"

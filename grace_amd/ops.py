@@ -288,6 +288,18 @@ def fill(x, value):
     return x
 
 
+def fill_bf16(x, bits=0):
+    """x[:] = the bf16 with these 16 bits (grace_fill_bf16): a contiguous bfloat16 device tensor, or
+    view, at any 2-byte alignment and of any length."""
+    if not isinstance(x, torch.Tensor) or x.dtype != BF16 or not x.is_contiguous():
+        raise TypeError("grace_amd: fill_bf16 takes a contiguous bfloat16 tensor")
+    if x.device.type != "cuda":
+        raise GraceDeviceError(f"grace_amd: fill_bf16 takes a GPU tensor; got {x.device}")
+    if x.numel():   # (an empty tensor has no address to hand over)
+        _lib.call("grace_fill_bf16", _p(x), int(bits) & 0xFFFF, x.numel(), _stream())
+    return x
+
+
 def sum_rank_order(tensors):
     """Python ``sum(list)`` = ((0 + t0) + t1) + ... on the device (grace_dl/dist/__init__.py:32-34)."""
     first = dev_f32(tensors[0])
@@ -1365,24 +1377,38 @@ def shard_record_words(cap):
 SHARD_HDR = 8   # shard.hip kShHdr: header words (word 0 = the shard length)
 
 
+def _shard_out_fn(out, what, name):
+    """The entry point for this dense output's element type: `name` for float32, its _bf16 twin for
+    bfloat16 (the output holds bf16 bits); any other dtype, or a strided view, is refused here."""
+    if not isinstance(out, torch.Tensor) or out.dtype not in (F32, BF16) or not out.is_contiguous():
+        raise TypeError(f"grace_amd: {what}: out must be a contiguous float32 or bfloat16 tensor, got "
+                        f"{getattr(out, 'dtype', type(out))}")
+    return name if out.dtype == F32 else name + "_bf16"
+
+
 def shard_select(recs, world, rank, cap, tab, k, residual, out, out_base, pay_idx, status, sel_gi=None):
     """grace_shard_select over the W gathered records: the exact global top-k (dense output into the
     zero-filled `out`, which covers global [out_base, out_base + out.numel())), this rank's residual
     restored where the global cut rejects a local pick, pay_idx = global index or -1 per own entry.
     `status`: pinned int32 word (bit 1: a record's shard length differs from the agreed `tab`).
-    sel_gi: optional int32[world * cap] <- every entry's global index if selected, else -1."""
+    sel_gi: optional int32[world * cap] <- every entry's global index if selected, else -1.
+    `out` is float32, or bfloat16 (grace_shard_select_bf16: every selected value rounded once to
+    nearest even); everything else keeps its type."""
     dev = recs.device
+    fn = _shard_out_fn(out, "shard_select", "grace_shard_select")
     if sel_gi is not None and (sel_gi.dtype != torch.int32 or sel_gi.numel() < int(world) * int(cap)):
         raise ValueError("shard_select: sel_gi must be int32 with world * cap elements")
     ws = workspace("shardsel", _lib.query("grace_shard_select_workspace_bytes", int(world), int(cap)), dev)
-    _lib.call("grace_shard_select", _p(recs), int(world), int(rank), int(cap), _p(tab), int(k), _p(residual),
+    _lib.call(fn, _p(recs), int(world), int(rank), int(cap), _p(tab), int(k), _p(residual),
               _p(out), int(out_base), out.numel(), _p(pay_idx), _p(sel_gi), _p(ws), ws.numel(), status.data_ptr(),
               _stream())
 
 
 def shard_clear(out, out_base, sel_gi):
-    """Zero the positions a previous shard_select wrote (its sel_gi) in a recycled output."""
-    _lib.call("grace_shard_clear", _p(out), int(out_base), out.numel(), _p(sel_gi), sel_gi.numel(), _stream())
+    """Zero the positions a previous shard_select wrote (its sel_gi) in a recycled output (float32
+    or bfloat16, as shard_select)."""
+    fn = _shard_out_fn(out, "shard_clear", "grace_shard_clear")
+    _lib.call(fn, _p(out), int(out_base), out.numel(), _p(sel_gi), sel_gi.numel(), _stream())
     return out
 
 

@@ -110,6 +110,10 @@ grace_status_t grace_sub(const float* t, const float* d, float* r, int64_t n, vo
 /* out = x / divisor  (Communicator average: allgather.py:45, allreduce.py:12) */
 grace_status_t grace_div_scalar(const float* x, float divisor, float* out, int64_t n, void* stream);
 grace_status_t grace_fill(float* x, float value, int64_t n, void* stream);
+/* x[i] = bits for n 2-byte elements (the zero-fill of a bfloat16 dense output: bits = 0): x at any
+ * 2-byte alignment, any n >= 0; 16-B non-temporal stores over the whole 16-B lines, element stores
+ * before the first and after the last */
+grace_status_t grace_fill_bf16(uint16_t* x, uint16_t bits, int64_t n, void* stream);
 /* HBM ceiling probe for bench.py (no reference counterpart): r = r + g, o = 0 with non-temporal 16-B
    loads / stores (the top-k step's 2-read / 2-write dense traffic, none of its arithmetic).
    variant 0-2: chunks of 8192 / 12288 / 16384 elements per workgroup; 3-5: grid-stride over
@@ -632,6 +636,17 @@ grace_status_t grace_shard_select(const int32_t* recs, int32_t world, int32_t ra
                                   void* stream);
 grace_status_t grace_shard_clear(float* out, int64_t out_base, int64_t out_len, const int32_t* sel_gi, int64_t count,
                                  void* stream);
+/* The select and the clear with a bfloat16 dense output (out holds bf16 bits; grace_amd/sharded_bf16.py):
+ * the same arguments, limits and checks.  out[gi - out_base] = bf16(0 + v), rounded once to nearest
+ * even as grace_f32_to_bf16 rounds (a NaN becomes 0x7FC0), written as a 2-byte store; the clear
+ * stores a 2-byte zero.  The records, the residual, pay_idx, sel_gi and the status word are exactly
+ * what grace_shard_select leaves: only the element type of `out` differs. */
+grace_status_t grace_shard_select_bf16(const int32_t* recs, int32_t world, int32_t rank, int64_t cap,
+                                       const int64_t* tab, int64_t k, float* residual, uint16_t* out, int64_t out_base,
+                                       int64_t out_len, int32_t* pay_idx, int32_t* sel_gi, void* ws, size_t ws_bytes,
+                                       int32_t* status_host, void* stream);
+grace_status_t grace_shard_clear_bf16(uint16_t* out, int64_t out_base, int64_t out_len, const int32_t* sel_gi,
+                                      int64_t count, void* stream);
 
 /* ---- DGC (grace_dl/dist/compressor/dgc.py:12-50, memory/dgc.py:15-39) -------------------------
  * compress: grace_dgc_sample (|t| at the sampled indices: sample_idx from the caller = torch's

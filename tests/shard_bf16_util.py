@@ -1,6 +1,7 @@
 """One process plays all W ranks of the sharded top-k step on one device (test infrastructure for
 tests/test_gpu_sharded_bf16.py): every rank's local swap step writes its slot of ONE records buffer
 (what the all-gather would deliver), then ops.shard_select runs for each rank over all of them."""
+import numpy as np
 import torch
 
 from grace_amd import ops
@@ -55,16 +56,28 @@ class Ranks:
             new.append(out)
         return new
 
-    def select(self, res, outs, out_base=None):
-        """ops.shard_select for every rank into outs[r] (pre-filled by the caller; out_base[r] = the
-        global index of its first element, 0 when None), on COPIES of the residuals `res`.
-        Returns (the residual copies, pay_idx per rank, sel_gi per rank)."""
+    def set_records(self, vals_u32, li, hdr=None):
+        """Hand-built records (tests/shard_select_util.py): value bits uint32[W, cap] and local
+        indices int32[W, cap] as numpy arrays; header word 0 of rank w = hdr[w] (default its shard
+        length), the other header words 0."""
+        rec = np.zeros((self.world, self.stride), dtype=np.int32)
+        rec[:, 0] = self.sizes if hdr is None else hdr
+        rec[:, ops.SHARD_HDR:ops.SHARD_HDR + self.cap] = np.ascontiguousarray(vals_u32, dtype=np.uint32).view(np.int32)
+        rec[:, ops.SHARD_HDR + self.cap:] = li
+        self.recs.copy_(torch.from_numpy(rec).view(-1))
+
+    def select(self, res, outs, out_base=None, k=None, ranks=None, sel_gi=True):
+        """ops.shard_select for every rank (or for `ranks`) into outs[r] (pre-filled by the caller;
+        out_base[r] = the global index of its first element, 0 when None), on COPIES of the
+        residuals `res` (explicit tensors per rank: a list, or a dict by rank), with this
+        partition's k or the call's own; sel_gi=False passes no selection list.
+        Returns (the residual copies, pay_idx, sel_gi or None), one entry per rank run, in order."""
         rs, pays, sels = [], [], []
-        for r in range(self.world):
+        for r in range(self.world) if ranks is None else ranks:
             rr = res[r].clone()
             pay = torch.full((self.cap,), -1, dtype=torch.int32, device=self.dev)
-            sel = torch.full((self.world * self.cap,), -2, dtype=torch.int32, device=self.dev)
-            ops.shard_select(self.recs, self.world, r, self.cap, self.tab, self.k, rr, outs[r],
+            sel = torch.full((self.world * self.cap,), -2, dtype=torch.int32, device=self.dev) if sel_gi else None
+            ops.shard_select(self.recs, self.world, r, self.cap, self.tab, self.k if k is None else k, rr, outs[r],
                              0 if out_base is None else out_base[r], pay, self.status, sel)
             rs.append(rr)
             pays.append(pay)

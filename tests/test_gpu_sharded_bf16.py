@@ -21,6 +21,7 @@ import torch.multiprocessing as mp
 from oracle import grace_oracle as O
 from tests.golden_util import same_bits
 from tests.shard_bf16_util import BF16, CANARY, Ranks, bits16, from_bits16, same_i32
+from tests.shard_select_util import round_cpu as _round_cpu
 from tests.test_sharded_bf16_gloo import _bucket as bf16_bucket
 from tests.test_sharded_bf16_gloo import _check_step
 
@@ -46,17 +47,6 @@ def _sizes(n, world):
 def _zeros16(n, dev):
     from grace_amd import ops
     return ops.fill_bf16(torch.empty(n, dtype=BF16, device=dev), 0)
-
-
-def _round_cpu(out32):
-    """The f32 dense result rounded once, on the CPU: the reference of every bf16 output here.
-    torch's CPU cast rounds to nearest even; what it makes of a NaN depends on the build (its
-    vectorised path gives 0xFFFF), so a NaN position is held to the pattern the kernels define,
-    0x7FC0 exactly -- not merely to being a NaN."""
-    x = out32.detach().cpu()
-    b = bits16(x.to(BF16))
-    b[torch.isnan(x)] = 0x7FC0
-    return b
 
 
 # ------------------------------------------------------------------ 1. the select, every store site

@@ -16,6 +16,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from oracle import grace_oracle as O
+from tests.shard_select_util import ref_select
 
 HDR = 8
 
@@ -46,27 +47,15 @@ class OracleShardKernels:
     def select(self, recs, world, rank, cap, tab, k, res, out, out_base, pay_idx, status):
         rv = recs.numpy().reshape(world, HDR + 2 * cap)
         tb = tab.numpy()
-        sizes, bases = tb[:world], tb[world:]
-        if any(int(rv[w, 0]) != int(sizes[w]) for w in range(world)):
+        ref = ref_select(rv[:, HDR:HDR + cap].copy().view(np.uint32), rv[:, HDR + cap:], tb[:world], tb[world:],
+                         rv[:, 0], k, rank, out_base, out.numel())
+        if ref["status"] & 1:
             status[0] |= 1
-        li = rv[:, HDR + cap:].astype(np.int64)
-        v = rv[:, HDR:HDR + cap].copy().view(np.float32)
-        gi = li + bases[:, None]
-        valid = li >= 0
-        keys = O.abs_key(v).astype(np.int64)
-        flat = np.nonzero(valid.ravel())[0]
-        order = np.lexsort((gi.ravel()[flat], -keys.ravel()[flat]))[:k]
-        sel = np.zeros(world * cap, dtype=bool)
-        sel[flat[order]] = True
-        sel = sel.reshape(world, cap)
         o = out.numpy()
-        q = gi[sel] - out_base
-        ok = (q >= 0) & (q < o.size)
-        o[q[ok]] = np.float32(0.0) + v[sel][ok]
-        p = pay_idx.numpy()
-        p[:] = np.where(sel[rank], gi[rank], -1).astype(np.int32)
-        rej = valid[rank] & ~sel[rank]
-        res.numpy()[li[rank][rej]] = v[rank][rej]
+        o[ref["out_pos"]] = ref["out_f32"][ref["out_pos"]]
+        pay_idx.numpy()[:] = ref["pay_idx"]
+        at, bits = ref["restore"]
+        res.numpy()[at] = bits.view(np.float32)
 
     def new_status(self, device):
         return torch.zeros(1, dtype=torch.int32)

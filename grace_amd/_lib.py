@@ -1,4 +1,5 @@
-"""ctypes binding of libgrace_hip.so (the C ABI declared in include/grace_hip.h).
+"""ctypes binding of libgrace_hip.so (the C ABI declared in include/grace_hip.h and
+include/grace_hip_sign.h).
 
 The library is the only compute path of grace_amd: there is no CPU or eager-PyTorch fallback.
 If the shared object is missing (not built) or a tensor is not on the GPU, calls raise.
@@ -184,6 +185,22 @@ SIGNATURES = {
     "grace_normal_fill": (ST, [P, I64, U64, P]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/grace_hip_sign.h (the sign family on
+# bfloat16 and the fused EF-signSGD step; a bf16 array is passed as the address of its 16-bit words)
+SIGNATURES_SIGN = {
+    "grace_efsign_workspace_bytes": (SZ, [I64]),
+    "grace_efsign_step": (ST, [P, P, I32, F32, I64, P, P, P, F32, P, SZ, P]),
+    "grace_efsign_step_bf16": (ST, [P, P, I32, F32, I64, P, P, P, F32, P, SZ, P]),
+    "grace_efsign_decode_aggregate": (ST, [P, P, I32, F32, P, I64, P]),
+    "grace_efsign_decode_aggregate_bf16": (ST, [P, P, I32, F32, P, I64, P]),
+    "grace_sign_encode_bf16": (ST, [P, P, I64, P]),
+    "grace_sign_encode_bits_bf16": (ST, [P, I64, P, P]),
+    "grace_sign_step_w1_bf16": (ST, [P, P, P, I64, P]),
+    "grace_sign_majority_bf16": (ST, [P, I32, P, I64, P]),
+    "grace_sign_majority_bits_bf16": (ST, [P, I64, I32, I64, P, P]),
+    "grace_signum_encode_bf16": (ST, [P, P, I32, F32, F32, P, I64, P]),
+}
+
 
 class GraceNativeError(RuntimeError):
     """A native call failed or the native library is unavailable."""
@@ -205,7 +222,7 @@ def load():
                     f"grace_amd native library not found at {LIB_PATH}; build it with "
                     "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
             lib = ctypes.CDLL(LIB_PATH)
-            for name, (res, args) in SIGNATURES.items():
+            for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items()):
                 fn = getattr(lib, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -225,7 +242,7 @@ def use(path):
         lib = _handles.get(path)
         if lib is None:
             lib = ctypes.CDLL(os.path.abspath(path))
-            for name, (res, args) in SIGNATURES.items():
+            for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items()):
                 f = getattr(lib, name, None)
                 if f is not None:
                     f.restype = res

@@ -25,7 +25,7 @@ FLAGS = [
 
 
 def _newest_dep():
-    deps = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(ROOT, "include", "grace_hip.h")]
+    deps = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(ROOT, "include", "*.h"))
     return max(os.path.getmtime(d) for d in deps)
 
 

@@ -160,11 +160,21 @@ REUSE_OK = _refcount_selftest()
 
 
 _sign_w1 = None
+_sign_w1_bf16 = None
 
 
 def launch_sign_step_w1(x, out):
-    """grace_sign_step_w1 on a contiguous f32 device tensor into `out`: the launch-bound W=1 path."""
-    global _sign_w1
+    """grace_sign_step_w1 on a contiguous f32 device tensor into `out`: the launch-bound W=1 path.
+    A bfloat16 x (and out) goes to grace_sign_step_w1_bf16."""
+    global _sign_w1, _sign_w1_bf16
+    if x.dtype is BF16:
+        f = _sign_w1_bf16
+        if f is None:
+            f = _sign_w1_bf16 = _lib.fn("grace_sign_step_w1_bf16")
+        st = f(x.data_ptr(), None, out.data_ptr(), x.numel(), _stream())
+        if st:
+            _lib.check("grace_sign_step_w1_bf16", st)
+        return
     f = _sign_w1
     if f is None:
         f = _sign_w1 = _lib.fn("grace_sign_step_w1")
@@ -320,10 +330,21 @@ def _out_buf(out, n, dtype, device, what):
     return out
 
 
+def _entry(name, dtype):
+    """The entry point of `name` for a gradient or dense result of this dtype (f32 or bf16)."""
+    return name if dtype == F32 else name + "_bf16"
+
+
+def _dense_dtype(out_dtype, what):
+    if out_dtype != F32 and out_dtype != BF16:
+        raise TypeError(f"grace_amd: {what}: out_dtype must be float32 or bfloat16, got {out_dtype}")
+    return out_dtype
+
+
 def sign_encode(x, out=None):
-    x = dev_f32(x)
+    x = dev_grad(x, "tensor")
     codes = _out_buf(out, x.numel(), torch.uint8, x.device, "sign_encode")
-    _lib.call("grace_sign_encode", _p(x), _p(codes), x.numel(), _stream())
+    _lib.call(_entry("grace_sign_encode", x.dtype), _p(x), _p(codes), x.numel(), _stream())
     return codes
 
 
@@ -335,30 +356,80 @@ def sign_decode(codes, scale=None):
     return out
 
 
-def sign_majority(codes_wn, world, n):
+def sign_majority(codes_wn, world, n, out_dtype=F32):
+    """The vote as +-1 in out_dtype (float32, or bfloat16: 0x3F80 / 0xBF80)."""
+    out_dtype = _dense_dtype(out_dtype, "sign_majority")
     codes_wn = require_dev(codes_wn, "codes")
-    out = torch.empty(n, dtype=F32, device=codes_wn.device)
-    _lib.call("grace_sign_majority", _p(codes_wn), int(world), _p(out), n, _stream())
+    out = torch.empty(n, dtype=out_dtype, device=codes_wn.device)
+    _lib.call(_entry("grace_sign_majority", out_dtype), _p(codes_wn), int(world), _p(out), n, _stream())
     return out
 
 
 def signum_encode(g, momentum_buf, has_prev, momentum):
-    g = dev_f32(g)
+    """g is f32 or bf16; the momentum buffer is f32 either way (bit-equal for g and g.float())."""
+    g = dev_grad(g)
+    if g.dtype == BF16 and not _f32_residual(momentum_buf, g.numel(), g.device):
+        raise TypeError("grace_amd: signum_encode: the momentum of a bfloat16 gradient must be a contiguous float32 "
+                        f"tensor of {g.numel()} elements on {g.device}")
     codes = torch.empty(g.numel(), dtype=torch.uint8, device=g.device)
     coef_g = float(torch.tensor(1.0 - momentum, dtype=F32))     # Python double, rounded as torch does
     coef_m = float(torch.tensor(momentum, dtype=F32))
-    _lib.call("grace_signum_encode", _p(g), _p(momentum_buf), 1 if has_prev else 0, coef_g, coef_m,
+    _lib.call(_entry("grace_signum_encode", g.dtype), _p(g), _p(momentum_buf), 1 if has_prev else 0, coef_g, coef_m,
               _p(codes), g.numel(), _stream())
     return codes
 
 
 def sign_step_w1(x, want_codes=True, reuse_out=False):
+    """(codes or None, +-1 in x's dtype and shape); x is f32 or bf16."""
     if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == F32 and x.is_contiguous()):
-        x = dev_f32(x)   # (the checks dev_f32 would make, without its reshape on the common path)
+        x = dev_grad(x, "tensor")   # (the checks on the common path, without the reshape)
     codes = torch.empty(x.numel(), dtype=torch.uint8, device=x.device) if want_codes else None
-    out = reusable_output("sign_w1", x.shape, F32, x.device) if reuse_out else torch.empty_like(x)
-    _lib.call("grace_sign_step_w1", x.data_ptr(), _p(codes), out.data_ptr(), x.numel(), _stream())
+    out = reusable_output("sign_w1", x.shape, x.dtype, x.device) if reuse_out else torch.empty_like(x)
+    _lib.call(_entry("grace_sign_step_w1", x.dtype), x.data_ptr(), _p(codes), out.data_ptr(), x.numel(), _stream())
     return codes, out
+
+
+def efsign_step(g, residual, has_residual, lr_mem, lr_agg, *, want_codes, out=None):
+    """One fused EF-signSGD step of this rank (grace_efsign_step): g is f32 or
+    bf16 and is only read; `residual` (f32, g's length) is read when has_residual and receives r' in
+    place -- on a name's first step it is the new buffer to write into.  Returns (mean f32[1], the u8
+    codes or None, out or None): `out`, when given, receives the world-1 dense result
+    (0 + dec) / lr_agg in g's dtype.  The mean is the one the device used for r' and out."""
+    g = dev_grad(g)
+    n = g.numel()
+    if not _f32_residual(residual, n, g.device):
+        raise TypeError(f"grace_amd: efsign_step: residual must be a contiguous float32 tensor of {n} elements on "
+                        f"{g.device}")
+    if out is not None:
+        out = _bf16_out(out, n, g.device, "efsign_step") if g.dtype == BF16 else \
+            _out_buf(out, n, F32, g.device, "efsign_step")
+    mean = torch.empty(1, dtype=F32, device=g.device)
+    codes = torch.empty(n, dtype=torch.uint8, device=g.device) if want_codes else None
+    if n:
+        nbytes = _lib.query("grace_efsign_workspace_bytes", n)
+        ws = workspace("efsign", nbytes, g.device)
+        _lib.call(_entry("grace_efsign_step", g.dtype), _p(g), _p(residual), 1 if has_residual else 0, float(lr_mem), n,
+                  _p(mean), _p(codes), _p(out), float(lr_agg), _p(ws), nbytes, _stream())
+    return mean, codes, out
+
+
+def efsign_decode_aggregate(means, codes, world, n, lr_agg, out_dtype=F32):
+    """(((0 + m_0 d_0) + m_1 d_1) + ...) / lr_agg over `world` gathered EF-signSGD payloads (means
+    f32[world], codes u8[world * n] rank-major), in out_dtype: one launch, one rounding."""
+    out_dtype = _dense_dtype(out_dtype, "efsign_decode_aggregate")
+    world, n = int(world), int(n)
+    for t, dtype, count, what in ((means, F32, world, "means"), (codes, torch.uint8, world * n, "codes")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != count or not t.is_contiguous():
+            raise TypeError(f"grace_amd: efsign_decode_aggregate: {what} must be a contiguous {dtype} tensor of "
+                            f"{count} elements")
+    if world < 1:
+        raise ValueError("grace_amd: efsign_decode_aggregate: world must be at least 1")
+    means, codes = require_dev(means, "means"), require_dev(codes, "codes")
+    out = torch.empty(n, dtype=out_dtype, device=codes.device)
+    if n:
+        _lib.call(_entry("grace_efsign_decode_aggregate", out_dtype), _p(means), _p(codes), world, float(lr_agg),
+                  _p(out), n, _stream())
+    return out
 
 
 def abs_mean(x):
@@ -1598,11 +1669,12 @@ def pack_bits(codes):
 
 
 def sign_encode_bits(x):
-    """sign codes (x >= 0) of a f32 device tensor straight into int32 words (the pack_bits layout)."""
-    x = dev_f32(x)
+    """sign codes (x >= 0) of a f32 or bf16 device tensor straight into int32 words (the pack_bits
+    layout)."""
+    x = dev_grad(x, "tensor")
     n = x.numel()
     words = torch.empty((n + 31) // 32, dtype=torch.int32, device=x.device)
-    _lib.call("grace_sign_encode_bits", _p(x), n, _p(words), _stream())
+    _lib.call(_entry("grace_sign_encode_bits", x.dtype), _p(x), n, _p(words), _stream())
     return words
 
 
@@ -1613,10 +1685,12 @@ def unpack_bits(words, n):
     return codes
 
 
-def sign_majority_bits(words_wn, world, n):
+def sign_majority_bits(words_wn, world, n, out_dtype=F32):
+    out_dtype = _dense_dtype(out_dtype, "sign_majority_bits")
     words_wn = require_dev(words_wn, "words")
-    out = torch.empty(n, dtype=F32, device=words_wn.device)
-    _lib.call("grace_sign_majority_bits", _p(words_wn), (n + 31) // 32, int(world), n, _p(out), _stream())
+    out = torch.empty(n, dtype=out_dtype, device=words_wn.device)
+    _lib.call(_entry("grace_sign_majority_bits", out_dtype), _p(words_wn), (n + 31) // 32, int(world), n, _p(out),
+              _stream())
     return out
 
 

@@ -1,5 +1,5 @@
-"""ctypes binding of libgrace_hip.so (the C ABI declared in include/grace_hip.h and
-include/grace_hip_sign.h).
+"""ctypes binding of libgrace_hip.so (the C ABI declared in include/grace_hip.h,
+include/grace_hip_sign.h and include/grace_hip_quant.h).
 
 The library is the only compute path of grace_amd: there is no CPU or eager-PyTorch fallback.
 If the shared object is missing (not built) or a tensor is not on the GPU, calls raise.
@@ -201,6 +201,17 @@ SIGNATURES_SIGN = {
     "grace_signum_encode_bf16": (ST, [P, P, I32, F32, F32, P, I64, P]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/grace_hip_quant.h (QSGD and TernGrad on
+# bfloat16: each entry point has its f32 form's argument list)
+SIGNATURES_QUANT = {
+    "grace_qsgd_compress_at_bf16": SIGNATURES["grace_qsgd_compress_at"],
+    "grace_qsgd_step_w1_bf16": SIGNATURES["grace_qsgd_step_w1"],
+    "grace_qsgd_decompress_bf16": SIGNATURES["grace_qsgd_decompress"],
+    "grace_terngrad_compress_bf16": SIGNATURES["grace_terngrad_compress"],
+    "grace_terngrad_step_w1_bf16": SIGNATURES["grace_terngrad_step_w1"],
+    "grace_terngrad_decompress_bf16": SIGNATURES["grace_terngrad_decompress"],
+}
+
 
 class GraceNativeError(RuntimeError):
     """A native call failed or the native library is unavailable."""
@@ -222,7 +233,7 @@ def load():
                     f"grace_amd native library not found at {LIB_PATH}; build it with "
                     "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
             lib = ctypes.CDLL(LIB_PATH)
-            for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items()):
+            for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items(), *SIGNATURES_QUANT.items()):
                 fn = getattr(lib, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -242,7 +253,7 @@ def use(path):
         lib = _handles.get(path)
         if lib is None:
             lib = ctypes.CDLL(os.path.abspath(path))
-            for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items()):
+            for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items(), *SIGNATURES_QUANT.items()):
                 f = getattr(lib, name, None)
                 if f is not None:
                     f.restype = res

@@ -13,6 +13,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "../../include/grace_hip_quant.h"
 
 namespace grace {
 
@@ -82,6 +83,31 @@ __device__ __forceinline__ int32_t f2i16_x86(float v) {
 }
 
 typedef float f4v __attribute__((ext_vector_type(4)));
+typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+
+// The element type of a gradient or a dense result: float, or bfloat16 as its 16 bits (uint16_t,
+// DESIGN.md section 11).  A quad is four consecutive elements as they sit in memory (16 B / 8 B): the
+// pipelined kernels keep prefetched quads in this form and widen them where they are used, so no
+// conversion stands between a load and the work it overlaps.  Widening is exact; narrowing rounds
+// once (common.h f32_to_bf16).  For float every member is the identity.
+template <typename T> struct Elem;
+template <> struct Elem<float> {
+  using quad = f4v;
+  __device__ static __forceinline__ f4v widen(f4v q) { return q; }
+  __device__ static __forceinline__ float widen1(float v) { return v; }
+  __device__ static __forceinline__ float narrow1(float v) { return v; }
+  __device__ static __forceinline__ f4v narrow(f4v o) { return o; }
+};
+template <> struct Elem<uint16_t> {
+  using quad = u2v;
+  __device__ static __forceinline__ f4v widen(u2v w) {
+    return f4v{u2f(w.x << 16), u2f(w.x & 0xFFFF0000u), u2f(w.y << 16), u2f(w.y & 0xFFFF0000u)};
+  }
+  __device__ static __forceinline__ float widen1(uint16_t b) { return bf16_to_f32(b); }
+  __device__ static __forceinline__ uint16_t narrow1(float v) { return f32_to_bf16(v); }
+  __device__ static __forceinline__ u2v narrow(f4v o) { return u2v{pack_bf16x2(o.x, o.y), pack_bf16x2(o.z, o.w)}; }
+};
+template <typename T> using quad_t = typename Elem<T>::quad;
 
 // 4 consecutive floats from p[e .. e+3], zero past `end`; one 16-B load when aligned and full
 __device__ __forceinline__ void load_quad(const float* __restrict__ p, int64_t e, int64_t end, bool aligned,
@@ -205,12 +231,12 @@ __device__ __forceinline__ void uniform01x4_k(uint64_t key, uint32_t i, float (&
 // FUSED: the world-1 Allgather step (qsgd.py:41-51 decompress, allgather.py:44 sum from 0, division by
 // 1 omitted) in the same pass: out = 0 + (norm / q) * code, written instead of the codes and norms --
 // the same arithmetic as qsgd_decode_bkt_kernel, so the result is bit-identical to compress + decode.
-template <typename CodeT, int VARIANT, bool FUSED = false>
+template <typename CodeT, int VARIANT, bool FUSED = false, typename XT = float>
 __global__ __launch_bounds__(kQBlock) void qsgd_encode128_kernel(
-    const float* __restrict__ x, const int64_t* __restrict__ seg_off, const int64_t* __restrict__ bkt_off,
+    const XT* __restrict__ x, const int64_t* __restrict__ seg_off, const int64_t* __restrict__ bkt_off,
     int nseg, int32_t nbuckets, float qf, const float* __restrict__ u, uint64_t seed,
     const float* __restrict__ norms_in, float* __restrict__ norms_out, CodeT* __restrict__ codes,
-    float* __restrict__ fused_out = nullptr, uint32_t xoff = 0) {
+    XT* __restrict__ fused_out = nullptr, uint32_t xoff = 0) {
   // xoff: the bucket element of x[0] for the device generator (a shard of a larger bucket,
   // grace_qsgd_compress_at): the draws are keyed by the bucket's element index
   __shared__ SegTables32 tab;
@@ -231,6 +257,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_kernel(
   for (int32_t b = b_first; b < bhi; b += kQNB * kRows) {
     int32_t bb[kQNB], e[kQNB][2], end[kQNB];
     bool ok[kQNB], fast[kQNB][2];
+    quad_t<XT> raw[kQNB][2];
     float v[kQNB][2][4];
 #pragma unroll
     for (int h = 0; h < kQNB; ++h) {
@@ -245,17 +272,24 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_kernel(
         fast[h][q] = ok[h] && (base & 3) == 0 && e[h][q] + 3 < end[h];
         // unconditional 16-B load (element 0 stands in for a slow quad): a load under a divergent
         // branch makes the compiler wait vmcnt(0) at the join, serialising the loads
-        const f4v t = *reinterpret_cast<const f4v*>(x + (fast[h][q] ? e[h][q] : 0));
-        v[h][q][0] = t.x; v[h][q][1] = t.y; v[h][q][2] = t.z; v[h][q][3] = t.w;
+        raw[h][q] = *reinterpret_cast<const quad_t<XT>*>(x + (fast[h][q] ? e[h][q] : 0));
       }
     }
+#pragma unroll
+    for (int h = 0; h < kQNB; ++h)   // widened once every load is issued (bf16; nothing to do for f32)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const f4v t = Elem<XT>::widen(raw[h][q]);
+        v[h][q][0] = t.x; v[h][q][1] = t.y; v[h][q][2] = t.z; v[h][q][3] = t.w;
+      }
 #pragma unroll
     for (int h = 0; h < kQNB; ++h)   // quads at a segment edge / unaligned segment (rare)
 #pragma unroll
       for (int q = 0; q < 2; ++q)
         if (!fast[h][q]) {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) v[h][q][j] = ok[h] && e[h][q] + j < end[h] ? x[e[h][q] + j] : 0.f;
+          for (int j = 0; j < 4; ++j)
+            v[h][q][j] = ok[h] && e[h][q] + j < end[h] ? Elem<XT>::widen1(x[e[h][q] + j]) : 0.f;
         }
     float norm[kQNB];
     if (norms_in) {
@@ -313,11 +347,12 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_kernel(
             o[j] = 0.f + d;
           }
           if (fast[h][q]) {
-            __builtin_nontemporal_store(f4v{o[0], o[1], o[2], o[3]}, reinterpret_cast<f4v*>(fused_out + eq));
+            __builtin_nontemporal_store(Elem<XT>::narrow(f4v{o[0], o[1], o[2], o[3]}),
+                                        reinterpret_cast<quad_t<XT>*>(fused_out + eq));
           } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-              if (eq + j < end[h]) fused_out[eq + j] = o[j];
+              if (eq + j < end[h]) fused_out[eq + j] = Elem<XT>::narrow1(o[j]);
           }
         } else if (kStage16 && st16[h]) {
           cst[threadIdx.x >> 4][h * 32 + q * 16 + l16] =
@@ -366,12 +401,12 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_kernel(
 constexpr int kQEncPipeGridCap = 4096;   // A/B on the ResNet-50 set: 1024 35.6, 2048 34.6, 4096 34.2 us
 constexpr int kQBkMax = 1024;   // buckets per workgroup of the pipelined encoder (its LDS table)
 
-template <typename CodeT, int VARIANT, bool FUSED>
+template <typename CodeT, int VARIANT, bool FUSED, typename XT = float>
 struct QsgdPipe {
   static constexpr bool kStage16 = !FUSED && sizeof(CodeT) == 1;
   static constexpr int kRows = kQBlock / 16;
   struct Tile {
-    f4v v[kQNB][2];
+    quad_t<XT> v[kQNB][2];   // as loaded; widened in encode()
     int32_t base[kQNB], bb[kQNB];
     bool full[kQNB];
   };
@@ -403,12 +438,12 @@ struct QsgdPipe {
   }
 };
 
-template <typename CodeT, int VARIANT, bool FUSED = false>
+template <typename CodeT, int VARIANT, bool FUSED = false, typename XT = float>
 __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
-    const float* __restrict__ x, const int64_t* __restrict__ seg_off, const int64_t* __restrict__ bkt_off,
+    const XT* __restrict__ x, const int64_t* __restrict__ seg_off, const int64_t* __restrict__ bkt_off,
     int nseg, int32_t nbuckets, float qf, uint64_t seed, float* __restrict__ norms_out,
-    CodeT* __restrict__ codes, float* __restrict__ fused_out) {
-  using P = QsgdPipe<CodeT, VARIANT, FUSED>;
+    CodeT* __restrict__ codes, XT* __restrict__ fused_out) {
+  using P = QsgdPipe<CodeT, VARIANT, FUSED, XT>;
   using Tile = typename P::Tile;
   constexpr int kRows = P::kRows;
   constexpr int kStride = kQNB * kRows;
@@ -456,7 +491,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
       for (int q = 0; q < 2; ++q) {
         int32_t e = full ? base + 4 * l16 + 64 * q : 0;
         asm volatile("" : "+v"(e));   // opaque: hipcc would otherwise split the load into a branch
-        T.v[h][q] = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(x + e));
+        T.v[h][q] = __builtin_nontemporal_load(reinterpret_cast<const quad_t<XT>*>(x + e));
       }
     }
   };
@@ -468,7 +503,8 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
       acc[h] = 0.0;
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
-        const float v4[4] = {T.v[h][q][0], T.v[h][q][1], T.v[h][q][2], T.v[h][q][3]};
+        const f4v w4 = Elem<XT>::widen(T.v[h][q]);
+        const float v4[4] = {w4[0], w4[1], w4[2], w4[3]};
         acc[h] = P::sq_acc(v4, acc[h]);
       }
       acc[h] = row16_sum(acc[h]);
@@ -511,6 +547,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int32_t eq = base + 4 * l16 + 64 * q;
+        const f4v xq = Elem<XT>::widen(T.v[h][q]);
         float uu[4];
         P::uniform4(bc + (uint32_t)(64 * q) * kC, klo, khi, uu);
         CodeT c[4];
@@ -523,7 +560,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
           int32_t ni[4];
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const float xv = T.v[h][q][j];
+            const float xv = xq[j];
             const float level = scale[h] * fabsf(xv);
             const float prev = floorf(level);
             const float nl = uu[j] < level - prev ? prev + 1.0f : prev;
@@ -536,7 +573,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
         } else {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const float xv = T.v[h][q][j];
+            const float xv = xq[j];
             const float level = scale[h] * fabsf(xv);   // VARIANT 1: scale = q / norm
             c[j] = qsgd_code<CodeT, VARIANT>(xv, level, uu[j], norm[h]);
             cf[j] = (float)c[j];
@@ -553,7 +590,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
             if (VARIANT == 1 && cf[j] == -128.0f) d = __int_as_float(0x7FC00000);
             o[j] = 0.f + d;
           }
-          __builtin_nontemporal_store(o, reinterpret_cast<f4v*>(fused_out + eq));
+          __builtin_nontemporal_store(Elem<XT>::narrow(o), reinterpret_cast<quad_t<XT>*>(fused_out + eq));
         } else if (kStage16 && st16) {
           cst[row][h * 32 + q * 16 + l16] = cw;
         } else if constexpr (sizeof(CodeT) == 1) {
@@ -601,7 +638,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
     for (int q = 0; q < 2; ++q) {
       const int32_t eq = base + 4 * l16 + 64 * q;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v[q][j] = eq + j < end ? x[eq + j] : 0.f;
+      for (int j = 0; j < 4; ++j) v[q][j] = eq + j < end ? Elem<XT>::widen1(x[eq + j]) : 0.f;
       acc = P::sq_acc(v[q], acc);
     }
     const float norm = P::bucket_norm(acc);
@@ -626,7 +663,7 @@ __global__ __launch_bounds__(kQBlock) void qsgd_encode128_pipe_kernel(
           const float cf = (float)c[j];
           float d = dsc * cf;
           if (VARIANT == 1 && cf == -128.0f) d = __int_as_float(0x7FC00000);
-          fused_out[eq + j] = 0.f + d;
+          fused_out[eq + j] = Elem<XT>::narrow1(0.f + d);
         } else {
           codes[eq + j] = c[j];
         }
@@ -875,12 +912,12 @@ struct QShardRec {
   const int64_t* lo;   // rank_lo[w]: the first element of rank w's range
 };
 
-template <typename CodeT, int VARIANT>
+template <typename CodeT, int VARIANT, typename OT = float>
 __global__ __launch_bounds__(kQBlock) void qsgd_decode_bkt_kernel(
     const CodeT* __restrict__ codes, const float* __restrict__ norms, int64_t code_stride,
     int64_t norm_stride, int world, const int64_t* __restrict__ seg_off,
     const int64_t* __restrict__ bkt_off, int nseg, float qf, float divisor, int aggregate, int vec,
-    float* __restrict__ out, QShardRec sr = QShardRec{0, 0, 0, 0, nullptr}) {
+    OT* __restrict__ out, QShardRec sr = QShardRec{0, 0, 0, 0, nullptr}) {
   __shared__ SegTables32 tab;
   stage_tables32(tab, seg_off, bkt_off, nseg);
   const int l16 = threadIdx.x & 15;
@@ -961,11 +998,12 @@ __global__ __launch_bounds__(kQBlock) void qsgd_decode_bkt_kernel(
         }
         const int32_t eq = e[h][q];
         if (full[h][q]) {
-          __builtin_nontemporal_store(f4v{a4[0], a4[1], a4[2], a4[3]}, reinterpret_cast<f4v*>(out + eq));
+          __builtin_nontemporal_store(Elem<OT>::narrow(f4v{a4[0], a4[1], a4[2], a4[3]}),
+                                      reinterpret_cast<quad_t<OT>*>(out + eq));
         } else {
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            if (eq + j < end[h]) out[eq + j] = a4[j];
+            if (eq + j < end[h]) out[eq + j] = Elem<OT>::narrow1(a4[j]);
         }
       }
     }
@@ -1054,7 +1092,8 @@ __host__ __device__ inline size_t tern_ws_bytes(int64_t nunits) { return sizeof(
 // segment's partials itself.
 // unit0 / xoff (sharded TernGrad, grace_terngrad_shard_*): this launch runs the global units unit0,
 // unit0 + 1, ... and x points at global element xoff (its shard); 0 / 0 for a whole bucket
-__global__ __launch_bounds__(kQBlock) void tern_stats_kernel(const float* __restrict__ x,
+template <typename XT = float>
+__global__ __launch_bounds__(kQBlock) void tern_stats_kernel(const XT* __restrict__ x,
                                                             const int64_t* __restrict__ seg_off,
                                                             const int64_t* __restrict__ unit_off, int nseg,
                                                             const float* __restrict__ clip_in, TernSlot* __restrict__ w,
@@ -1072,13 +1111,13 @@ __global__ __launch_bounds__(kQBlock) void tern_stats_kernel(const float* __rest
   float amax = 0.f;
   uint32_t nan = 0;
   const int t = threadIdx.x;
-  if (base + t < qs.a0) tern_acc(x[base + t], sum, sq, amax, nan);
-  if (qs.a1 + t < end) tern_acc(x[qs.a1 + t], sum, sq, amax, nan);
-  const f4v* xq = reinterpret_cast<const f4v*>(x + qs.a0);
+  if (base + t < qs.a0) tern_acc(Elem<XT>::widen1(x[base + t]), sum, sq, amax, nan);
+  if (qs.a1 + t < end) tern_acc(Elem<XT>::widen1(x[qs.a1 + t]), sum, sq, amax, nan);
+  const quad_t<XT>* xq = reinterpret_cast<const quad_t<XT>*>(x + qs.a0);
   const int64_t nq = (qs.a1 - qs.a0) >> 2;
 #pragma unroll 4
   for (int64_t j = t; j < nq; j += kQBlock) {
-    const f4v v = xq[j];   // a plain load (allocates in the caches): the encoder re-reads x (A/B: -4 %)
+    const f4v v = Elem<XT>::widen(xq[j]);   // a plain load (allocates in the caches): the encoder re-reads x (A/B: -4 %)
     tern_acc(v.x, sum, sq, amax, nan);
     tern_acc(v.y, sum, sq, amax, nan);
     tern_acc(v.z, sum, sq, amax, nan);
@@ -1095,11 +1134,11 @@ constexpr int kTernBlock = 256;   // encode workgroup (A/B: 256 beats 512 and 10
 // HAS_U: an injected uniform stream (parity tests); a separate instantiation, so the device-
 // generator path has no load under a branch (hipcc would wait vmcnt(0) at the join, i.e. also for
 // the prefetched next sub-chunk)
-template <bool FUSED = false, bool HAS_U = false>
+template <bool FUSED = false, bool HAS_U = false, typename XT = float>
 __global__ __launch_bounds__(kTernBlock) void tern_encode_kernel(
-    const float* __restrict__ x, const int64_t* __restrict__ seg_off, const int64_t* __restrict__ unit_off,
+    const XT* __restrict__ x, const int64_t* __restrict__ seg_off, const int64_t* __restrict__ unit_off,
     int nseg, const TernSlot* __restrict__ w, const float* __restrict__ u, uint64_t seed,
-    int8_t* __restrict__ codes, float* __restrict__ out, const float* __restrict__ clip_in,
+    int8_t* __restrict__ codes, XT* __restrict__ out, const float* __restrict__ clip_in,
     float* __restrict__ scalars, int64_t unit0 = 0, int64_t xoff = 0) {
   __shared__ SegTables tab;
   const SegView sv = stage_tables(tab, seg_off, unit_off, nseg);
@@ -1123,8 +1162,9 @@ __global__ __launch_bounds__(kTernBlock) void tern_encode_kernel(
   constexpr int kTernSub = 4;
   constexpr int kTernSteps = kPer / kTernSub;
   static_assert(kPer % kTernSub == 0, "sub-chunks tile the unit");
-  const f4v* xq = reinterpret_cast<const f4v*>(x + qs.a0);
-  auto load_sub = [&](int st, f4v (&dst)[kTernSub]) {
+  using XQ = quad_t<XT>;   // sub-chunks stay as loaded; encode_quad widens them
+  const XQ* xq = reinterpret_cast<const XQ*>(x + qs.a0);
+  auto load_sub = [&](int st, XQ (&dst)[kTernSub]) {
 #pragma unroll
     for (int k = 0; k < kTernSub; ++k) {
       const int64_t j = t + (int64_t)(st * kTernSub + k) * kTernBlock;
@@ -1134,7 +1174,7 @@ __global__ __launch_bounds__(kTernBlock) void tern_encode_kernel(
       if (nq > 0) dst[k] = xq[j < nq ? j : 0];
     }
   };
-  f4v cur[kTernSub], nxt[kTernSub];
+  XQ cur[kTernSub], nxt[kTernSub];
   load_sub(0, cur);
   float c, scalar;
   {
@@ -1173,7 +1213,7 @@ __global__ __launch_bounds__(kTernBlock) void tern_encode_kernel(
     return code;
   };
   auto put1 = [&](int64_t i, int8_t cd) {
-    if constexpr (FUSED) out[i] = 0.f + (float)cd * scalar;
+    if constexpr (FUSED) out[i] = Elem<XT>::narrow1(0.f + (float)cd * scalar);
     else codes[i] = cd;
   };
   // The device generator draws a quad's four uniforms at once (uniform01x4 at the GLOBAL quad index,
@@ -1199,11 +1239,11 @@ __global__ __launch_bounds__(kTernBlock) void tern_encode_kernel(
   };
   if (base + t < qs.a0) {
     const int64_t i = base + t;
-    put1(i, enc(x[i], HAS_U ? u[i] : u1(i)));
+    put1(i, enc(Elem<XT>::widen1(x[i]), HAS_U ? u[i] : u1(i)));
   }
   if (qs.a1 + t < end) {
     const int64_t i = qs.a1 + t;
-    put1(i, enc(x[i], HAS_U ? u[i] : u1(i)));
+    put1(i, enc(Elem<XT>::widen1(x[i]), HAS_U ? u[i] : u1(i)));
   }
   // The quads: the same codes as enc() with fewer instructions.  With s = scalar > 0 (then
   // c >= scalar > 0): enc() is sign(x) where u s < min(|x|, c) and 0 elsewhere (x = +-0 never
@@ -1222,7 +1262,8 @@ __global__ __launch_bounds__(kTernBlock) void tern_encode_kernel(
     }
     return cw;
   };
-  auto encode_quad = [&](int jq, const f4v& v) {
+  auto encode_quad = [&](int jq, const XQ& vraw) {
+    const f4v v = Elem<XT>::widen(vraw);
     const int64_t i = qs.a0 + 4 * (int64_t)jq;
     f4v uu;
     if constexpr (HAS_U) {
@@ -1249,7 +1290,7 @@ __global__ __launch_bounds__(kTernBlock) void tern_encode_kernel(
       f4v o;
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] = 0.f + (float)(int8_t)(uint8_t)(cw >> (8 * j)) * scalar;
-      __builtin_nontemporal_store(o, reinterpret_cast<f4v*>(out + i));
+      __builtin_nontemporal_store(Elem<XT>::narrow(o), reinterpret_cast<XQ*>(out + i));
     } else {
       *reinterpret_cast<uint32_t*>(codes + i) = cw;
     }
@@ -1258,8 +1299,8 @@ __global__ __launch_bounds__(kTernBlock) void tern_encode_kernel(
   const int nqi = (int)nq;
 #pragma unroll
   for (int st = 0; st < kTernSteps; ++st) {
-    f4v (&curb)[kTernSub] = (st & 1) ? nxt : cur;
-    f4v (&nxtb)[kTernSub] = (st & 1) ? cur : nxt;
+    XQ (&curb)[kTernSub] = (st & 1) ? nxt : cur;
+    XQ (&nxtb)[kTernSub] = (st & 1) ? cur : nxt;
     if (st + 1 < kTernSteps) load_sub(st + 1, nxtb);
 #pragma unroll
     for (int k = 0; k < kTernSub; ++k) {
@@ -1397,6 +1438,106 @@ __global__ __launch_bounds__(kQBlock) void tern_decode_row_kernel(const int8_t* 
     }
   }
 }
+
+// tern_decode_row_kernel with the quotient rounded once to bfloat16 (8-B stores): the same rows, loads
+// and arithmetic.  A copy, not a template over the output type: as a template, or as a wrapper
+// around a shared body, the f32 kernel lost its place in the module or its register allocation, and
+// with the first a dozen other f32 kernels changed their code for find_seg32 (hipcc 7.2).  Keep the
+// two in step.
+__global__ __launch_bounds__(kQBlock) void tern_decode_row_bf16_kernel(const int8_t* __restrict__ codes,
+                                                                      const float* __restrict__ scalars,
+                                                                      int64_t code_stride, int64_t scal_stride,
+                                                                      int world, const int64_t* __restrict__ seg_off,
+                                                                      int nseg, int32_t n, float divisor,
+                                                                      int aggregate, int vec,
+                                                                      uint16_t* __restrict__ out) {
+  using OT = uint16_t;
+  __shared__ int32_t seg[kSegLds + 1];
+  for (int i = threadIdx.x; i <= nseg; i += blockDim.x) seg[i] = (int32_t)seg_off[i];
+  __syncthreads();
+  const int l16 = threadIdx.x & 15;
+  constexpr int kRows = kQBlock / 16;
+  const int32_t nchunks = (n + 127) / 128;
+  int32_t blo, bhi;
+  block_range32(nchunks, kRows, blo, bhi);
+  const int32_t c_first = blo + (int32_t)(threadIdx.x >> 4);
+  int s = c_first < bhi ? find_seg32(seg, nseg, c_first * 128) : 0;
+  for (int32_t c = c_first; c < bhi; c += kQNB * kRows) {
+    int32_t e[kQNB][2], ce[kQNB];
+    int sidx[kQNB];
+    bool ok[kQNB], full[kQNB][2];
+#pragma unroll
+    for (int h = 0; h < kQNB; ++h) {
+      const int32_t cc = c + h * kRows;
+      ok[h] = cc < bhi;
+      const int32_t i0 = cc * 128;
+      if (ok[h]) s = seg_advance32(seg, nseg, s, i0);
+      sidx[h] = s;
+      ce[h] = ok[h] ? min(i0 + 128, n) : i0;
+      const bool uni = seg[s + 1] >= ce[h];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        e[h][q] = i0 + 4 * l16 + 64 * q;
+        full[h][q] = ok[h] && uni && vec && e[h][q] + 3 < ce[h];
+      }
+    }
+    float acc[kQNB][2][4] = {};
+    for (int w = 0; w < world; ++w) {
+      float cv[kQNB][2][4], sc[kQNB];
+#pragma unroll
+      for (int h = 0; h < kQNB; ++h) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+          load_codes4(codes + (full[h][q] ? w * code_stride + e[h][q] : 0), true, cv[h][q]);
+        sc[h] = scalars[w * scal_stride + sidx[h]];
+      }
+#pragma unroll
+      for (int h = 0; h < kQNB; ++h)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          if (full[h][q]) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const float d = cv[h][q][j] * sc[h];
+              acc[h][q][j] = (aggregate || w > 0) ? acc[h][q][j] + d : d;
+            }
+          } else if (ok[h]) {   // chunk edge / segment boundary / unaligned codes: per element
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const int32_t i = e[h][q] + j;
+              if (i < ce[h]) {
+                const int sj = seg_advance32(seg, nseg, sidx[h], i);
+                const float d = (float)codes[w * code_stride + i] * scalars[w * scal_stride + sj];
+                acc[h][q][j] = (aggregate || w > 0) ? acc[h][q][j] + d : d;
+              }
+            }
+          }
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < kQNB; ++h) {
+      if (!ok[h]) continue;
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        float* a4 = acc[h][q];
+        if (divisor != 1.0f) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) a4[j] = a4[j] / divisor;
+        }
+        const int32_t eq = e[h][q];
+        if (full[h][q]) {
+          __builtin_nontemporal_store(Elem<OT>::narrow(f4v{a4[0], a4[1], a4[2], a4[3]}),
+                                      reinterpret_cast<quad_t<OT>*>(out + eq));
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (eq + j < ce[h]) out[eq + j] = Elem<OT>::narrow1(a4[j]);
+        }
+      }
+    }
+  }
+}
+
 
 __device__ __attribute__((noinline)) void tern_decode_slow(const int8_t* __restrict__ codes,
                                                            const float* __restrict__ scalars, int64_t code_stride,
@@ -1969,11 +2110,11 @@ grace_status_t grace_qsgd_compress_at(const float* x, int64_t xoff, const int64_
     const unsigned grid16 = pipe ? qenc_pipe_grid(nbuckets) : stream_grid(nbuckets, kQNB * kQBlock / 16, kQEncGridCap);
 #define GRACE_QENC128(CT, V)                                                                         \
   do { if (pipe)                                                                                          \
-    qsgd_encode128_pipe_kernel<CT, V><<<grid16, kQBlock, 0, st>>>(x, seg_off, bkt_off, nseg, (int32_t)nbuckets, \
+    qsgd_encode128_pipe_kernel<CT, V, false, float><<<grid16, kQBlock, 0, st>>>(x, seg_off, bkt_off, nseg, (int32_t)nbuckets, \
                                                                (float)quantum_num, seed, norms_out,  \
                                                                reinterpret_cast<CT*>(codes), nullptr); \
   else                                                                                               \
-    qsgd_encode128_kernel<CT, V><<<grid16, kQBlock, 0, st>>>(x, seg_off, bkt_off, nseg, (int32_t)nbuckets, \
+    qsgd_encode128_kernel<CT, V, false, float><<<grid16, kQBlock, 0, st>>>(x, seg_off, bkt_off, nseg, (int32_t)nbuckets, \
                                                           (float)quantum_num, u, seed, norms_in,      \
                                                           norms_out, reinterpret_cast<CT*>(codes),    \
                                                           nullptr, (uint32_t)xoff); } while (0)
@@ -2143,10 +2284,10 @@ grace_status_t grace_terngrad_compress(const float* x, const int64_t* seg_off, c
                                                                        scalars);
   GRACE_CHECK_LAUNCH("grace_terngrad_compress");
   if (u)
-    tern_encode_kernel<false, true><<<(unsigned)nunits, kTernBlock, 0, as_stream(stream)>>>(
+    tern_encode_kernel<false, true, float><<<(unsigned)nunits, kTernBlock, 0, as_stream(stream)>>>(
         x, seg_off, unit_off, nseg, w, u, seed, codes, nullptr, clip_in, scalars);
   else
-    tern_encode_kernel<false, false><<<(unsigned)nunits, kTernBlock, 0, as_stream(stream)>>>(
+    tern_encode_kernel<false, false, float><<<(unsigned)nunits, kTernBlock, 0, as_stream(stream)>>>(
         x, seg_off, unit_off, nseg, w, u, seed, codes, nullptr, clip_in, scalars);
   GRACE_CHECK_LAUNCH("grace_terngrad_compress");
   return GRACE_OK;
@@ -2178,10 +2319,10 @@ grace_status_t grace_terngrad_shard_encode(const float* x, int64_t xoff, const i
   if (nunits_local == 0) return GRACE_OK;
   const TernSlot* w = reinterpret_cast<const TernSlot*>(ws);
   if (u)
-    tern_encode_kernel<false, true><<<(unsigned)nunits_local, kTernBlock, 0, as_stream(stream)>>>(
+    tern_encode_kernel<false, true, float><<<(unsigned)nunits_local, kTernBlock, 0, as_stream(stream)>>>(
         x, seg_off, unit_off, nseg, w, u, seed, codes, nullptr, clip_in, nullptr, unit0, xoff);
   else
-    tern_encode_kernel<false, false><<<(unsigned)nunits_local, kTernBlock, 0, as_stream(stream)>>>(
+    tern_encode_kernel<false, false, float><<<(unsigned)nunits_local, kTernBlock, 0, as_stream(stream)>>>(
         x, seg_off, unit_off, nseg, w, u, seed, codes, nullptr, clip_in, nullptr, unit0, xoff);
   GRACE_CHECK_LAUNCH("grace_terngrad_shard_encode");
   return GRACE_OK;
@@ -2338,6 +2479,156 @@ grace_status_t grace_fp16_decompress_aggregate(const void* half_in, int64_t stri
   f16_to_f32_kernel<<<stream_grid((n + 3) / 4, kQBlock, 4096), kQBlock, 0, as_stream(stream)>>>(
       reinterpret_cast<const __half*>(half_in), out, n, al, stride, world, 1, divisor);
   GRACE_CHECK_LAUNCH("grace_fp16_decompress_aggregate");
+  return GRACE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// bfloat16 twins (include/grace_hip_quant.h): the same kernels instantiated on
+// 16-bit elements, the fast paths only.  Codes, norms and scalars are the f32 entry points' for the
+// widened gradient; a dense result is the f32 result rounded once.
+static inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline bool qsgd_fast(int32_t nseg, int64_t nbuckets, int32_t quantum_num, int32_t variant) {
+  return nseg >= 1 && nseg <= kSegLds && nbuckets >= 0 && nbuckets < (int64_t(1) << 24) && quantum_num >= 1 &&
+         (variant == 0 || (variant == 1 && quantum_num < 128));
+}
+// n < 2^31 seen from the unit table: every unit but a segment's last holds kTernUnit elements
+static inline bool tern_fast(int32_t nseg, int64_t nunits) {
+  return nseg >= 1 && nseg <= kSegLds && nunits >= 1 && nunits <= ((int64_t(1) << 31) / kTernUnit) + nseg;
+}
+
+grace_status_t grace_qsgd_compress_at_bf16(const uint16_t* x, int64_t xoff, const int64_t* seg_off,
+                                           const int64_t* bkt_off, int32_t nseg, int64_t nbuckets,
+                                           int32_t quantum_num, int32_t bucket_size, int32_t variant, const float* u,
+                                           uint64_t seed, const float* norms_in, float* norms_out, void* codes,
+                                           void* stream) {
+  GRACE_REQUIRE(x && seg_off && bkt_off && norms_out && codes && xoff >= 0 && xoff < ((int64_t)1 << 31) &&
+                    bucket_size == 128 && qsgd_fast(nseg, nbuckets, quantum_num, variant) && al8(x),
+                "grace_qsgd_compress_at_bf16: bad arguments (bucket 128, <= 512 segments, < 2^24 buckets, "
+                "8-B aligned x)");
+  if (nbuckets == 0) return GRACE_OK;
+  hipStream_t st = as_stream(stream);
+  const bool pipe = !u && !norms_in && xoff == 0;
+  const unsigned grid16 = pipe ? qenc_pipe_grid(nbuckets) : stream_grid(nbuckets, kQNB * kQBlock / 16, kQEncGridCap);
+#define GRACE_QENC128B(CT, V)                                                                        \
+  do { if (pipe)                                                                                     \
+    qsgd_encode128_pipe_kernel<CT, V, false, uint16_t><<<grid16, kQBlock, 0, st>>>(                   \
+        x, seg_off, bkt_off, nseg, (int32_t)nbuckets, (float)quantum_num, seed, norms_out,           \
+        reinterpret_cast<CT*>(codes), (uint16_t*)nullptr);                                           \
+  else                                                                                               \
+    qsgd_encode128_kernel<CT, V, false, uint16_t><<<grid16, kQBlock, 0, st>>>(                        \
+        x, seg_off, bkt_off, nseg, (int32_t)nbuckets, (float)quantum_num, u, seed, norms_in, norms_out, \
+        reinterpret_cast<CT*>(codes), (uint16_t*)nullptr, (uint32_t)xoff); } while (0)
+  if (variant == 1) GRACE_QENC128B(int8_t, 1);
+  else if (quantum_num < 128) GRACE_QENC128B(int8_t, 0);
+  else GRACE_QENC128B(__half, 0);
+#undef GRACE_QENC128B
+  GRACE_CHECK_LAUNCH("grace_qsgd_compress_at_bf16");
+  return GRACE_OK;
+}
+
+grace_status_t grace_qsgd_step_w1_bf16(const uint16_t* x, const int64_t* seg_off, const int64_t* bkt_off,
+                                       int32_t nseg, int64_t nbuckets, int32_t quantum_num, int32_t variant,
+                                       const float* u, uint64_t seed, uint16_t* out, void* stream) {
+  GRACE_REQUIRE(x && seg_off && bkt_off && out && qsgd_fast(nseg, nbuckets, quantum_num, variant) && al8(x) &&
+                    al8(out),
+                "grace_qsgd_step_w1_bf16: bad arguments (bucket 128, <= 512 segments, < 2^24 buckets, 8-B aligned "
+                "x and out)");
+  if (nbuckets == 0) return GRACE_OK;
+  hipStream_t st = as_stream(stream);
+  const unsigned grid16 = stream_grid(nbuckets, kQNB * kQBlock / 16, kQEncGridCap);
+#define GRACE_QSTEP128B(CT, V)                                                                       \
+  qsgd_encode128_kernel<CT, V, true, uint16_t><<<grid16, kQBlock, 0, st>>>(                           \
+      x, seg_off, bkt_off, nseg, (int32_t)nbuckets, (float)quantum_num, u, seed, nullptr, nullptr,   \
+      (CT*)nullptr, out)
+  if (variant == 1) GRACE_QSTEP128B(int8_t, 1);
+  else if (quantum_num < 128) GRACE_QSTEP128B(int8_t, 0);
+  else GRACE_QSTEP128B(__half, 0);
+#undef GRACE_QSTEP128B
+  GRACE_CHECK_LAUNCH("grace_qsgd_step_w1_bf16");
+  return GRACE_OK;
+}
+
+grace_status_t grace_qsgd_decompress_bf16(const void* codes, const float* norms, int64_t code_stride,
+                                          int64_t norm_stride, int32_t world, const int64_t* seg_off,
+                                          const int64_t* bkt_off, int32_t nseg, int64_t n, int32_t quantum_num,
+                                          int32_t bucket_size, int32_t variant, int32_t aggregate, float divisor,
+                                          uint16_t* out, void* stream) {
+  GRACE_REQUIRE(codes && norms && seg_off && bkt_off && out && world >= 1 && nseg >= 1 && nseg <= kSegLds && n >= 0 &&
+                    n < (int64_t(1) << 31) && bucket_size == 128 && quantum_num >= 1 &&
+                    (variant == 0 || (variant == 1 && quantum_num < 128)) && al8(out),
+                "grace_qsgd_decompress_bf16: bad arguments (bucket 128, <= 512 segments, n < 2^31, 8-B aligned out)");
+  if (n == 0) return GRACE_OK;
+  const int64_t cbytes = variant == 0 && quantum_num >= 128 ? 2 : 1;
+  const int vec = (code_stride % 4 == 0) && ((uintptr_t)codes % (4 * cbytes) == 0);
+  const unsigned bgrid = stream_grid((n + 127) / 128 + nseg, kQNB * kQBlock / 16, kQGridCap);
+  hipStream_t st = as_stream(stream);
+#define GRACE_QDECBB(CT, V)                                                                          \
+  qsgd_decode_bkt_kernel<CT, V, uint16_t><<<bgrid, kQBlock, 0, st>>>(                                 \
+      reinterpret_cast<const CT*>(codes), norms, code_stride, norm_stride, world, seg_off, bkt_off, nseg, \
+      (float)quantum_num, divisor, aggregate, vec, out)
+  if (variant == 1) GRACE_QDECBB(int8_t, 1);
+  else if (quantum_num < 128) GRACE_QDECBB(int8_t, 0);
+  else GRACE_QDECBB(__half, 0);
+#undef GRACE_QDECBB
+  GRACE_CHECK_LAUNCH("grace_qsgd_decompress_bf16");
+  return GRACE_OK;
+}
+
+grace_status_t grace_terngrad_compress_bf16(const uint16_t* x, const int64_t* seg_off, const int64_t* unit_off,
+                                            int32_t nseg, int64_t nunits, const float* clip_in, const float* u,
+                                            uint64_t seed, int8_t* codes, float* scalars, void* ws, void* stream) {
+  GRACE_REQUIRE(x && seg_off && unit_off && codes && scalars && ws && tern_fast(nseg, nunits) && al8(x) && al16(u),
+                "grace_terngrad_compress_bf16: bad arguments (<= 512 segments, n < 2^31, 8-B aligned x, 16-B "
+                "aligned u)");
+  TernSlot* const w = reinterpret_cast<TernSlot*>(ws);
+  hipStream_t st = as_stream(stream);
+  tern_stats_kernel<uint16_t><<<(unsigned)nunits, kQBlock, 0, st>>>(x, seg_off, unit_off, nseg, clip_in, w, scalars);
+  GRACE_CHECK_LAUNCH("grace_terngrad_compress_bf16");
+  if (u)
+    tern_encode_kernel<false, true, uint16_t><<<(unsigned)nunits, kTernBlock, 0, st>>>(
+        x, seg_off, unit_off, nseg, w, u, seed, codes, (uint16_t*)nullptr, clip_in, scalars);
+  else
+    tern_encode_kernel<false, false, uint16_t><<<(unsigned)nunits, kTernBlock, 0, st>>>(
+        x, seg_off, unit_off, nseg, w, u, seed, codes, (uint16_t*)nullptr, clip_in, scalars);
+  GRACE_CHECK_LAUNCH("grace_terngrad_compress_bf16");
+  return GRACE_OK;
+}
+
+grace_status_t grace_terngrad_step_w1_bf16(const uint16_t* x, const int64_t* seg_off, const int64_t* unit_off,
+                                           int32_t nseg, int64_t nunits, const float* clip_in, const float* u,
+                                           uint64_t seed, float* scalars, void* ws, uint16_t* out, void* stream) {
+  GRACE_REQUIRE(x && seg_off && unit_off && scalars && ws && out && tern_fast(nseg, nunits) && al8(x) && al8(out) &&
+                    al16(u),
+                "grace_terngrad_step_w1_bf16: bad arguments (<= 512 segments, n < 2^31, 8-B aligned x and out, "
+                "16-B aligned u)");
+  TernSlot* const w = reinterpret_cast<TernSlot*>(ws);
+  hipStream_t st = as_stream(stream);
+  tern_stats_kernel<uint16_t><<<(unsigned)nunits, kQBlock, 0, st>>>(x, seg_off, unit_off, nseg, clip_in, w, scalars);
+  GRACE_CHECK_LAUNCH("grace_terngrad_step_w1_bf16");
+  if (u)
+    tern_encode_kernel<true, true, uint16_t><<<(unsigned)nunits, kTernBlock, 0, st>>>(
+        x, seg_off, unit_off, nseg, w, u, seed, nullptr, out, clip_in, scalars);
+  else
+    tern_encode_kernel<true, false, uint16_t><<<(unsigned)nunits, kTernBlock, 0, st>>>(
+        x, seg_off, unit_off, nseg, w, u, seed, nullptr, out, clip_in, scalars);
+  GRACE_CHECK_LAUNCH("grace_terngrad_step_w1_bf16");
+  return GRACE_OK;
+}
+
+grace_status_t grace_terngrad_decompress_bf16(const int8_t* codes, const float* scalars, int64_t code_stride,
+                                              int64_t scal_stride, int32_t world, const int64_t* seg_off,
+                                              int32_t nseg, int64_t n, int32_t aggregate, float divisor,
+                                              uint16_t* out, void* stream) {
+  GRACE_REQUIRE(codes && scalars && seg_off && out && world >= 1 && nseg >= 1 && nseg <= kSegLds && n >= 0 &&
+                    n < (int64_t(1) << 31) && al8(out),
+                "grace_terngrad_decompress_bf16: bad arguments (<= 512 segments, n < 2^31, 8-B aligned out)");
+  if (n == 0) return GRACE_OK;
+  const int vec = (code_stride % 4 == 0) && ((uintptr_t)codes % 4 == 0);
+  tern_decode_row_bf16_kernel<<<stream_grid((n + 127) / 128, kQNB * kQBlock / 16, kQGridCap), kQBlock, 0,
+                                as_stream(stream)>>>(codes, scalars, code_stride, scal_stride, world, seg_off, nseg,
+                                                     (int32_t)n, divisor, aggregate, vec, out);
+  GRACE_CHECK_LAUNCH("grace_terngrad_decompress_bf16");
   return GRACE_OK;
 }
 

@@ -939,21 +939,63 @@ def seg_tables(sizes, unit, device):
     return hit
 
 
+# ----------------------------------------------------------------------------- QSGD / TernGrad on bf16
+QUANT_SEG_MAX = 512   # quant.hip kSegLds (grace_qsgd_seg_max()): segments of the fast paths
+
+
+def _quant_grad(x, what, sizes, bucket_size=None):
+    """The flat gradient of a QSGD / TernGrad call: float32 (dev_f32, as ever) or bfloat16 (DESIGN.md
+    section 11).  Any other dtype is a TypeError before the device is looked at; a bf16 call outside
+    the fast paths' limits is a ValueError before any native call."""
+    if not isinstance(x, torch.Tensor) or x.dtype == F32:
+        return dev_f32(x)
+    if x.dtype != BF16:
+        raise TypeError(f"grace_amd: {what}: the gradient must be float32 or bfloat16, got {x.dtype}")
+    n = x.numel()
+    sizes = [n] if sizes is None else sizes
+    if len(sizes) > QUANT_SEG_MAX:
+        raise ValueError(f"grace_amd: {what}: a bfloat16 gradient takes at most {QUANT_SEG_MAX} segments, got "
+                         f"{len(sizes)}")
+    if bucket_size is None:
+        if n >= 2 ** 31:
+            raise ValueError(f"grace_amd: {what}: a bfloat16 gradient must have fewer than 2^31 elements, got {n}")
+    else:
+        if int(bucket_size) != 128:
+            raise ValueError(f"grace_amd: {what}: a bfloat16 gradient needs bucket_size 128, got {bucket_size}")
+        if sum((int(s) + 127) // 128 for s in sizes) >= 2 ** 24:
+            raise ValueError(f"grace_amd: {what}: a bfloat16 gradient must have fewer than 2^24 buckets")
+    x = dev_grad(x)
+    if x.data_ptr() % 8:
+        raise ValueError(f"grace_amd: {what}: a bfloat16 gradient must be 8-byte aligned")
+    return x
+
+
+def _quant_out(out_dtype, what, sizes, n, bucket_size=None):
+    """out_dtype of a decode: float32 or bfloat16 (TypeError otherwise); the bf16 decoders' limits."""
+    out_dtype = _dense_dtype(out_dtype, what)
+    if out_dtype == BF16:
+        if len(sizes) > QUANT_SEG_MAX or n >= 2 ** 31 or (bucket_size is not None and int(bucket_size) != 128):
+            raise ValueError(f"grace_amd: {what}: a bfloat16 result needs at most {QUANT_SEG_MAX} segments, fewer than "
+                             "2^31 elements" + (" and bucket_size 128" if bucket_size is not None else ""))
+    return out_dtype
+
+
 # ----------------------------------------------------------------------------- QSGD
 def qsgd_compress(x, quantum_num, bucket_size, sizes=None, variant=0, u=None, seed=0, norms_in=None, xoff=0,
                   codes_out=None, norms_out=None):
-    """x: flat f32 device buffer (one tensor, or `sizes` segments back to back).  xoff: the element
+    """x: flat f32 or bf16 device buffer (one tensor, or `sizes` segments back to back; bf16: bucket
+    128 only, the codes and norms of x.float()).  xoff: the element
     of a larger bucket x[0] is (a shard starting on a bucket boundary): the device generator draws
     by that bucket's element index (grace_qsgd_compress_at).  codes_out / norms_out: write there
     (views into a send record) instead of new tensors."""
-    x = dev_f32(x)
+    x = _quant_grad(x, "qsgd_compress", sizes, bucket_size)
     sizes = [x.numel()] if sizes is None else sizes
     seg_off, bkt_off, nb = seg_tables(sizes, bucket_size, x.device)
     codes = _out_buf(codes_out, x.numel(), torch.int8 if quantum_num < 128 else torch.float16, x.device,
                      "qsgd_compress")
     norms = _out_buf(norms_out, nb, F32, x.device, "qsgd_compress norms")
-    _lib.call("grace_qsgd_compress_at", _p(x), int(xoff), _p(seg_off), _p(bkt_off), len(sizes), nb, int(quantum_num),
-              int(bucket_size), int(variant), _p(u), seed64(seed), _p(norms_in), _p(norms),
+    _lib.call(_entry("grace_qsgd_compress_at", x.dtype), _p(x), int(xoff), _p(seg_off), _p(bkt_off), len(sizes), nb,
+              int(quantum_num), int(bucket_size), int(variant), _p(u), seed64(seed), _p(norms_in), _p(norms),
               _p(codes), _stream())
     return codes, norms
 
@@ -964,23 +1006,27 @@ def qsgd_step_w1_ok(sizes, bucket_size):
 
 def qsgd_step_w1(x, quantum_num, sizes=None, variant=0, u=None, seed=0):
     """World-1 Allgather(QSGD(q, bucket 128)).step in one pass (grace_qsgd_step_w1): the codes of
-    qsgd_compress decoded as (0 + d) / 1 without being stored; `sizes` segments as qsgd_compress."""
-    x = dev_f32(x)
+    qsgd_compress decoded as (0 + d) / 1 without being stored; `sizes` segments as qsgd_compress.
+    x is f32 or bf16; the result has x's dtype (bf16: the f32 result of x.float() rounded once)."""
+    x = _quant_grad(x, "qsgd_step_w1", sizes, 128)
     sizes = [x.numel()] if sizes is None else sizes
     seg_off, bkt_off, nb = seg_tables(sizes, 128, x.device)
-    out = torch.empty(x.numel(), dtype=F32, device=x.device)
-    _lib.call("grace_qsgd_step_w1", _p(x), _p(seg_off), _p(bkt_off), len(sizes), nb, int(quantum_num), int(variant),
-              _p(u), seed64(seed), _p(out), _stream())
+    out = torch.empty(x.numel(), dtype=x.dtype, device=x.device)
+    _lib.call(_entry("grace_qsgd_step_w1", x.dtype), _p(x), _p(seg_off), _p(bkt_off), len(sizes), nb, int(quantum_num),
+              int(variant), _p(u), seed64(seed), _p(out), _stream())
     return out
 
 
 def qsgd_decompress(codes, norms, quantum_num, bucket_size, n, sizes=None, variant=0, world=1,
-                    aggregate=False, divisor=1.0):
-    codes, norms = require_dev(codes), require_dev(norms)
+                    aggregate=False, divisor=1.0, out_dtype=F32):
+    """out_dtype bfloat16 (bucket 128 only): the f32 result, after the rank-ordered sum and the
+    division, rounded once."""
     sizes = [n] if sizes is None else sizes
+    out_dtype = _quant_out(out_dtype, "qsgd_decompress", sizes, n, bucket_size)
+    codes, norms = require_dev(codes), require_dev(norms)
     seg_off, bkt_off, nb = seg_tables(sizes, bucket_size, codes.device)
-    out = torch.empty(n, dtype=F32, device=codes.device)
-    _lib.call("grace_qsgd_decompress", _p(codes), _p(norms), n, nb, int(world), _p(seg_off), _p(bkt_off),
+    out = torch.empty(n, dtype=out_dtype, device=codes.device)
+    _lib.call(_entry("grace_qsgd_decompress", out_dtype), _p(codes), _p(norms), n, nb, int(world), _p(seg_off), _p(bkt_off),
               len(sizes), n, int(quantum_num), int(bucket_size), int(variant), 1 if aggregate else 0,
               float(divisor), _p(out), _stream())
     return out
@@ -1028,25 +1074,27 @@ def _tern_tables(sizes, n, device):
 
 
 def terngrad_compress(x, sizes=None, clip=None, u=None, seed=0):
-    x = dev_f32(x)
+    """x is f32 or bf16 (the codes and scalars of x.float())."""
+    x = _quant_grad(x, "terngrad_compress", sizes)
     sizes, seg_off, unit_off, nunits = _tern_tables(sizes, x.numel(), x.device)
     codes = torch.empty(x.numel(), dtype=torch.int8, device=x.device)
     scalars = torch.empty(len(sizes), dtype=F32, device=x.device)
     ws = workspace("terngrad", _lib.query("grace_terngrad_workspace_bytes", nunits), x.device)
-    _lib.call("grace_terngrad_compress", _p(x), _p(seg_off), _p(unit_off), len(sizes), nunits, _p(clip),
+    _lib.call(_entry("grace_terngrad_compress", x.dtype), _p(x), _p(seg_off), _p(unit_off), len(sizes), nunits, _p(clip),
               _p(u), seed64(seed), _p(codes), _p(scalars), _p(ws), _stream())
     return codes, scalars
 
 
 def terngrad_step_w1(x, sizes=None, clip=None, u=None, seed=0):
     """World-1 Allgather(TernGrad).step (grace_terngrad_step_w1): the statistics pass, then one pass
-    writing 0 + code * scalar for the codes terngrad_compress would draw, never storing them."""
-    x = dev_f32(x)
+    writing 0 + code * scalar for the codes terngrad_compress would draw, never storing them.
+    x is f32 or bf16; the result has x's dtype (bf16: the f32 result of x.float() rounded once)."""
+    x = _quant_grad(x, "terngrad_step_w1", sizes)
     sizes, seg_off, unit_off, nunits = _tern_tables(sizes, x.numel(), x.device)
     scalars = torch.empty(len(sizes), dtype=F32, device=x.device)
-    out = torch.empty(x.numel(), dtype=F32, device=x.device)
+    out = torch.empty(x.numel(), dtype=x.dtype, device=x.device)
     ws = workspace("terngrad", _lib.query("grace_terngrad_workspace_bytes", nunits), x.device)
-    _lib.call("grace_terngrad_step_w1", _p(x), _p(seg_off), _p(unit_off), len(sizes), nunits, _p(clip),
+    _lib.call(_entry("grace_terngrad_step_w1", x.dtype), _p(x), _p(seg_off), _p(unit_off), len(sizes), nunits, _p(clip),
               _p(u), seed64(seed), _p(scalars), _p(ws), _p(out), _stream())
     return out
 
@@ -1063,11 +1111,13 @@ def terngrad_decompress_records(records, rec_bytes, world, rank_lo, packed, scal
     return out
 
 
-def terngrad_decompress(codes, scalars, n, sizes=None, world=1, aggregate=False, divisor=1.0):
+def terngrad_decompress(codes, scalars, n, sizes=None, world=1, aggregate=False, divisor=1.0, out_dtype=F32):
+    """out_dtype bfloat16: the f32 result, after the rank-ordered sum and the division, rounded once."""
+    out_dtype = _quant_out(out_dtype, "terngrad_decompress", [n] if sizes is None else sizes, n)
     codes, scalars = require_dev(codes), require_dev(scalars)
     sizes, seg_off, _, _ = _tern_tables(sizes, n, codes.device)
-    out = torch.empty(n, dtype=F32, device=codes.device)
-    _lib.call("grace_terngrad_decompress", _p(codes), _p(scalars), n, len(sizes), int(world), _p(seg_off),
+    out = torch.empty(n, dtype=out_dtype, device=codes.device)
+    _lib.call(_entry("grace_terngrad_decompress", out_dtype), _p(codes), _p(scalars), n, len(sizes), int(world), _p(seg_off),
               len(sizes), n, 1 if aggregate else 0, float(divisor), _p(out), _stream())
     return out
 

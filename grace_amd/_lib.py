@@ -221,6 +221,17 @@ _lock = threading.Lock()
 _lib = None
 
 
+def _bind(lib, strict):
+    """Give every symbol of the three tables its restype and argtypes and return `lib`.  strict: a
+    symbol the library lacks raises AttributeError; otherwise it stays unbound."""
+    for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items(), *SIGNATURES_QUANT.items()):
+        f = getattr(lib, name) if strict else getattr(lib, name, None)
+        if f is not None:
+            f.restype = res
+            f.argtypes = args
+    return lib
+
+
 def load():
     """Load (once) and return the ctypes handle; raises GraceNativeError if it is missing."""
     global _lib
@@ -232,12 +243,7 @@ def load():
                 raise GraceNativeError(
                     f"grace_amd native library not found at {LIB_PATH}; build it with "
                     "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
-            lib = ctypes.CDLL(LIB_PATH)
-            for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items(), *SIGNATURES_QUANT.items()):
-                fn = getattr(lib, name)
-                fn.restype = res
-                fn.argtypes = args
-            _lib = lib
+            _lib = _bind(ctypes.CDLL(LIB_PATH), strict=True)
     return _lib
 
 
@@ -252,13 +258,7 @@ def use(path):
     with _lock:
         lib = _handles.get(path)
         if lib is None:
-            lib = ctypes.CDLL(os.path.abspath(path))
-            for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items(), *SIGNATURES_QUANT.items()):
-                f = getattr(lib, name, None)
-                if f is not None:
-                    f.restype = res
-                    f.argtypes = args
-            _handles[path] = lib
+            lib = _handles[path] = _bind(ctypes.CDLL(os.path.abspath(path)), strict=False)
         _lib = lib
         _fns.clear()
     return lib

@@ -21,18 +21,14 @@ TypeError.
 import torch
 
 from grace_amd import ops
-from grace_amd.dist.communicator.allgather import Allgather, _gather_flat
+from grace_amd._bf16 import bf16_on_allgather
+from grace_amd.dist.communicator.allgather import _gather_flat
 from grace_amd.dist.compressor.qsgd import QSGDCompressor as _F32QSGDCompressor
 from grace_amd.dist.compressor.qsgd import QSGDCompressor_CUDA as _F32QSGDCompressor_CUDA
 from grace_amd.dist.compressor.terngrad import TernGradCompressor as _F32TernGradCompressor
 from grace_amd.dist.memory.none import NoneMemory
 
 BF16 = torch.bfloat16
-
-
-def _bf16_step(communicator, tensor):
-    return (isinstance(communicator, Allgather) and type(communicator.memory) is NoneMemory
-            and isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.dtype == BF16)
 
 
 def _flat_aligned(tensor):
@@ -45,7 +41,7 @@ class _QSGDBf16:
     """fused_step of both QSGD flavours (mixed in ahead of the f32 class)."""
 
     def fused_step(self, communicator, tensor, name):
-        if not _bf16_step(communicator, tensor):
+        if not bf16_on_allgather(communicator, tensor, NoneMemory):
             return super().fused_step(communicator, tensor, name)
         if int(self.bucket_size) != 128:
             raise TypeError(f"grace_amd: QSGD on a bfloat16 gradient needs bucket_size 128, got {self.bucket_size} "
@@ -73,7 +69,7 @@ class QSGDCompressor_CUDA(_QSGDBf16, _F32QSGDCompressor_CUDA):
 class TernGradCompressor(_F32TernGradCompressor):
 
     def fused_step(self, communicator, tensor, name):
-        if not _bf16_step(communicator, tensor):
+        if not bf16_on_allgather(communicator, tensor, NoneMemory):
             return super().fused_step(communicator, tensor, name)
         g = _flat_aligned(tensor)
         n, world = g.numel(), int(communicator.world_size)

@@ -11,9 +11,9 @@ rank-ordered sum and the division, in the decode's epilogue.  A name whose gradi
 between steps keeps its residual and its carry (the carry layout does not depend on the dtype).
 """
 import torch
-import torch.distributed as dist
 
 from grace_amd import _lib, ops
+from grace_amd._bf16 import exchange_decode_sorted
 from grace_amd.dist.segmented import SegmentedTopK as _SegmentedTopK
 
 BF16 = torch.bfloat16
@@ -65,7 +65,8 @@ class SegmentedTopK(_SegmentedTopK):
         if total != n:
             raise ValueError("segment sizes do not add up to the buffer")
         res = self.residuals.get(name)
-        # always f32, never empty_like(g): the name keeps it if its gradient changes dtype
+        # always f32, never empty_like(g): the name keeps it if its gradient changes dtype (no contiguity
+        # test, as in the parent's rule: ops._f32_residual would restart a name the parent's rule keeps)
         has = res is not None and res.dtype == torch.float32 and res.numel() == n and res.device == g.device
         if not has:
             res = torch.empty(n, dtype=torch.float32, device=g.device)
@@ -103,19 +104,6 @@ class SegmentedTopK(_SegmentedTopK):
             self.local_step(flat, sizes, name, dense)
             return dense
         pay = self.local_step(flat, sizes, name, None)
-        k_total = pay.numel() // 2
-        divisor = W if self.average else 1
-        # (beyond the grouping's range, 2^28 elements: the f32 scatter decode, then one cast; too large a
-        # bucket for the test suite, so this branch is untested)
-        if n > ops.SORT_PAYLOAD_MAX_N:
-            gathered = torch.empty(W * 2 * k_total, dtype=torch.float32, device=pay.device)
-            dist.all_gather_into_tensor(gathered, pay)
-            dense = ops.sparse_aggregate(gathered, gathered[k_total:].view(torch.int32), 2 * k_total, [k_total] * W, W,
-                                         n, divisor)
-            return ops.f32_to_bf16(dense, out=out)
         # grouped by output chunk, one all-gather, and the decode that rounds ((0 + d_0) + d_1 + ...) / W
-        # once to bf16 and writes every element of `out` (payload.hip)
-        spay = ops.sort_payload(pay, k_total, n)
-        gathered = torch.empty(W * spay.numel(), dtype=torch.float32, device=pay.device)
-        dist.all_gather_into_tensor(gathered, spay)
-        return ops.sparse_aggregate_sorted(gathered, k_total, W, n, divisor, out_dtype=BF16, out=out)
+        # once to bf16 and writes every element of `out`
+        return exchange_decode_sorted(pay, pay.numel() // 2, n, W, W if self.average else 1, out)

@@ -21,7 +21,8 @@ unfused path.
 import torch
 
 from grace_amd import ops
-from grace_amd.dist.communicator.allgather import Allgather, _gather_flat
+from grace_amd._bf16 import bf16_on_allgather
+from grace_amd.dist.communicator.allgather import _gather_flat
 from grace_amd.dist.compressor.efsignsgd import EFSignSGDCompressor as _F32EFSignSGDCompressor
 from grace_amd.dist.compressor.signsgd import SignSGDCompressor as _F32SignSGDCompressor
 from grace_amd.dist.compressor.signum import SignumCompressor as _F32SignumCompressor
@@ -32,17 +33,12 @@ BF16 = torch.bfloat16
 F32 = torch.float32
 
 
-def _bf16_on_allgather(communicator, memory_type, tensor):
-    return (isinstance(communicator, Allgather) and type(communicator.memory) is memory_type
-            and isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.dtype == BF16)
-
-
 class SignSGDCompressor(_F32SignSGDCompressor):
     """`compress` is the parent's (ops.sign_encode / sign_encode_bits take bf16; `decompress` decodes
     to f32); the step on a bf16 tensor returns bf16 at every world size, with both wires."""
 
     def fused_step(self, communicator, tensor, name):
-        if not _bf16_on_allgather(communicator, NoneMemory, tensor):
+        if not bf16_on_allgather(communicator, tensor, NoneMemory):
             return super().fused_step(communicator, tensor, name)
         world = int(communicator.world_size)
         if world == 1:
@@ -77,7 +73,7 @@ class SignumCompressor(_F32SignumCompressor):
         return [codes], tensor.size()
 
     def fused_step(self, communicator, tensor, name):
-        if not _bf16_on_allgather(communicator, NoneMemory, tensor):
+        if not bf16_on_allgather(communicator, tensor, NoneMemory):
             return super().fused_step(communicator, tensor, name)
         world = int(communicator.world_size)
         (codes,), _ = self.compress(tensor, name)
@@ -90,7 +86,7 @@ class EFSignSGDCompressor(_F32EFSignSGDCompressor):
         """Allgather(EFSignSGDCompressor, EFSignSGDMemory).step on a bf16 tensor: the residual lives in
         memory.residuals[name] as f32 and is updated in place; any other triple or tensor is the
         parent's (an f32 gradient takes its unfused path, on the same residual)."""
-        if not _bf16_on_allgather(communicator, EFSignSGDMemory, tensor):
+        if not bf16_on_allgather(communicator, tensor, EFSignSGDMemory):
             return super().fused_step(communicator, tensor, name)
         mem = communicator.memory
         g = ops.dev_grad(tensor)

@@ -14,10 +14,9 @@ rounded once to nearest even -- at world > 1 after the rank-ordered sum and the 
 decode's epilogue (grace_sparse_aggregate_sorted_bf16).  float16 still raises TypeError.
 """
 import torch
-import torch.distributed as dist
 
 from grace_amd import ops
-from grace_amd.dist.communicator.allgather import Allgather
+from grace_amd._bf16 import bf16_on_allgather, exchange_decode_sorted
 from grace_amd.dist.compressor.topk import TopKCompressor as _F32TopKCompressor
 from grace_amd.dist.memory.none import NoneMemory
 from grace_amd.dist.memory.residual import ResidualMemory
@@ -37,39 +36,24 @@ class TopKCompressor(_F32TopKCompressor):
             ops.topk_check()
         return [vals, idx], tensor.size()
 
-    def _exchange_decode(self, buf, k, n, world):
-        """The world > 1 tail of a bf16 step: every rank's packed f32 payload `buf` -> the dense
-        rank-ordered aggregate, flat bf16, rounded once after the sum and the division."""
-        divisor = world if self.average else 1
-        if n > ops.SORT_PAYLOAD_MAX_N:
-            # beyond the index-sorted grouping's range (payload.hip): the rank-ordered scatter
-            # accumulates in its f32 output, so the result is narrowed in a second pass
-            gathered = torch.empty(world * 2 * k, dtype=torch.float32, device=buf.device)
-            dist.all_gather_into_tensor(gathered, buf)
-            out = ops.sparse_aggregate(gathered, gathered[k:].view(torch.int32), 2 * k, [k] * world, world, n,
-                                       divisor)
-            return ops.f32_to_bf16(out)
-        sbuf = ops.sort_payload(buf, k, n)
-        gathered = torch.empty(world * sbuf.numel(), dtype=torch.float32, device=buf.device)
-        dist.all_gather_into_tensor(gathered, sbuf)
-        return ops.sparse_aggregate_sorted(gathered, k, world, n, divisor, out_dtype=BF16)
-
     def _fused_step(self, communicator, tensor, name):
-        mem = communicator.memory
-        if not (isinstance(communicator, Allgather) and type(mem) in (NoneMemory, ResidualMemory)
-                and isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.dtype == BF16):
+        if not bf16_on_allgather(communicator, tensor, NoneMemory, ResidualMemory):
             return super()._fused_step(communicator, tensor, name)
+        mem = communicator.memory
         g = ops.dev_grad(tensor)
         n = g.numel()
         k = ops.ratio_k(n, self.compress_ratio)
         world = int(communicator.world_size)
+        divisor = world if self.average else 1
         if type(mem) is NoneMemory:
             if world == 1:   # payload and (0 + d) / 1 from one read of the tensor; never recycled
                 return ops.topk_step_dense(g, k)[3].view(tensor.shape)
             # the unfused path cannot return bf16 (ctx = tensor.size() carries no dtype)
             buf, _, _ = ops.topk_compress(g, k)
-            return self._exchange_decode(buf, k, n, world).view(tensor.shape)
+            return exchange_decode_sorted(buf, k, n, world, divisor).view(tensor.shape)
         # the residual is f32 whatever the gradient's dtype; one of another dtype or size does not count
+        # (no contiguity test, unlike ops._f32_residual: a strided f32 one counts here and is refused
+        # with ValueError by the step below, where that rule would restart the name without a word)
         res = mem.residuals.get(name)
         has = res is not None and res.dtype == torch.float32 and res.numel() == n and res.device == g.device
         if not has:
@@ -101,4 +85,4 @@ class TopKCompressor(_F32TopKCompressor):
                                                carry_valid=carry_valid)
             mem.residuals[name] = res
             mem.carry_written(name, res, carry)
-        return self._exchange_decode(buf, k, n, world).view(tensor.shape)
+        return exchange_decode_sorted(buf, k, n, world, divisor).view(tensor.shape)

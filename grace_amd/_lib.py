@@ -1,5 +1,5 @@
 """ctypes binding of libgrace_hip.so (the C ABI declared in include/grace_hip.h,
-include/grace_hip_sign.h and include/grace_hip_quant.h).
+include/grace_hip_sign.h, include/grace_hip_quant.h and include/grace_hip_dgc.h).
 
 The library is the only compute path of grace_amd: there is no CPU or eager-PyTorch fallback.
 If the shared object is missing (not built) or a tensor is not on the GPU, calls raise.
@@ -212,6 +212,19 @@ SIGNATURES_QUANT = {
     "grace_terngrad_decompress_bf16": SIGNATURES["grace_terngrad_decompress"],
 }
 
+# name -> (restype, argtypes); every symbol declared in include/grace_hip_dgc.h (DGC on bfloat16: the
+# twins have their f32 forms' argument lists; the records decode writes a bf16 dense result)
+SIGNATURES_DGC = {
+    "grace_dgc_step_w1_fused_bf16": SIGNATURES["grace_dgc_step_w1_fused"],
+    "grace_dgc_sample_comp_bf16": SIGNATURES["grace_dgc_sample_comp"],
+    "grace_dgc_compensate_bf16": SIGNATURES["grace_dgc_compensate"],
+    "grace_dgc_step_w1_bf16": SIGNATURES["grace_dgc_step_w1"],
+    "grace_sumsq_bf16": SIGNATURES["grace_sumsq"],
+    "grace_clip_by_sumsq_bf16": SIGNATURES["grace_clip_by_sumsq"],
+    "grace_sparse_aggregate_records_bf16_workspace_bytes": (SZ, [I32, I64]),
+    "grace_sparse_aggregate_records_bf16": (ST, [P, I64, I64, I32, F32, P, I64, P, P, SZ, P]),
+}
+
 
 class GraceNativeError(RuntimeError):
     """A native call failed or the native library is unavailable."""
@@ -222,9 +235,10 @@ _lib = None
 
 
 def _bind(lib, strict):
-    """Give every symbol of the three tables its restype and argtypes and return `lib`.  strict: a
+    """Give every symbol of the four tables its restype and argtypes and return `lib`.  strict: a
     symbol the library lacks raises AttributeError; otherwise it stays unbound."""
-    for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items(), *SIGNATURES_QUANT.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items(), *SIGNATURES_QUANT.items(),
+                              *SIGNATURES_DGC.items()):
         f = getattr(lib, name) if strict else getattr(lib, name, None)
         if f is not None:
             f.restype = res

@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "../../include/grace_hip_dgc.h"
 
 namespace grace {
 
@@ -31,6 +32,55 @@ constexpr int kNodes = (1 << (kDepth + 1)) - 1;   // 2047 thresholds the loop ca
 constexpr int kTab = 2048;              // sorted table (padded with +inf)
 constexpr int kDQ = 4;                  // quads per thread per round in the streaming passes
 typedef float f4d __attribute__((ext_vector_type(4)));
+
+// A gradient or a dense result is a float array or a bfloat16 one (its 16-bit words: widened
+// exactly, narrowed by common.h's integer round -- DESIGN.md §9, §12).  Quad<T> is the piece of a T
+// array beside one 16-B f32 quad -- 16 B of float, 8 B of bf16 -- held raw, so that a round's loads
+// are all issued before any is widened.  The float forms are the plain 16-B accesses the f32 kernels
+// always made: their code does not change (profiles/dgc_bf16_resource_usage.txt).
+// (A/B for the speculative pass, 2^26 elements, steady state: 8 B of bf16 beside each f32 quad, every
+// lane's elements the f32 kernel's, 279.5 us per step; 16 B of bf16 beside two f32 quads, a lane
+// owning 8 contiguous elements with its f32 accesses 32 B apart, 465.9 us -- profiles/dgc_bf16_bench.txt.)
+template <typename T> struct Quad;
+template <> struct Quad<float> {
+  typedef f4d raw;
+  static constexpr unsigned kMask = 15u;
+  static __device__ __forceinline__ f4d widen(raw v) { return v; }
+  static __device__ __forceinline__ raw narrow(f4d v) { return v; }
+};
+template <> struct Quad<uint16_t> {
+  typedef uint32_t raw __attribute__((ext_vector_type(2)));
+  static constexpr unsigned kMask = 7u;
+  static __device__ __forceinline__ f4d widen(raw v) {
+    f4d f = {u2f(v.x << 16), u2f(v.x & 0xFFFF0000u), u2f(v.y << 16), u2f(v.y & 0xFFFF0000u)};
+    return f;
+  }
+  static __device__ __forceinline__ raw narrow(f4d v) {
+    raw p = {pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)};
+    return p;
+  }
+};
+template <typename T>
+__device__ __forceinline__ bool alq(const T* p) { return (reinterpret_cast<uintptr_t>(p) & Quad<T>::kMask) == 0; }
+template <typename T>
+__device__ __forceinline__ typename Quad<T>::raw ldq(const T* p) {
+  return __builtin_nontemporal_load(reinterpret_cast<const typename Quad<T>::raw*>(p));
+}
+template <typename T>
+__device__ __forceinline__ void stq(f4d v, T* p) {
+  __builtin_nontemporal_store(Quad<T>::narrow(v), reinterpret_cast<typename Quad<T>::raw*>(p));
+}
+// the same by quad index q (elements 4 q .. 4 q + 3), the address form of the grid-stride kernels
+template <typename T>
+__device__ __forceinline__ typename Quad<T>::raw ldq(const T* p, int64_t q) {
+  return __builtin_nontemporal_load(reinterpret_cast<const typename Quad<T>::raw*>(p) + q);
+}
+template <typename T>
+__device__ __forceinline__ typename Quad<T>::raw* qptr(T* p) { return reinterpret_cast<typename Quad<T>::raw*>(p); }
+__device__ __forceinline__ float ld1(const float* p, int64_t i) { return p[i]; }
+__device__ __forceinline__ float ld1(const uint16_t* p, int64_t i) { return bf16_to_f32(p[i]); }
+__device__ __forceinline__ void st1(float* p, int64_t i, float v) { p[i] = v; }
+__device__ __forceinline__ void st1(uint16_t* p, int64_t i, float v) { p[i] = f32_to_bf16(v); }
 
 struct DgcMeta {
   uint32_t thr0;      // bits of the sampled threshold
@@ -115,7 +165,8 @@ __global__ __launch_bounds__(kDBlock) void dgc_sample_kernel(const float* __rest
 
 // the same sample of the compensated tensor t = a + (m r + g) (t = g on a name's first step), read
 // from the memory state BEFORE compensation: the world-1 fused step samples without materialising t
-__global__ __launch_bounds__(kDBlock) void dgc_sample_comp_kernel(const float* __restrict__ g,
+template <typename GT = float>
+__global__ __launch_bounds__(kDBlock) void dgc_sample_comp_kernel(const GT* __restrict__ g,
                                                                  const float* __restrict__ r,
                                                                  const float* __restrict__ a, int has_state,
                                                                  float momentum, int64_t n,
@@ -128,7 +179,7 @@ __global__ __launch_bounds__(kDBlock) void dgc_sample_comp_kernel(const float* _
     } else {
       i = dgc_sample_index(seed, j, n);
     }
-    const float gv = g[i];
+    const float gv = ld1(g, i);
     float rv = has_state ? r[i] : 0.f, av = has_state ? a[i] : 0.f;
     dgc_comp1(gv, rv, av, has_state, momentum);
     out[j] = fabsf(av);
@@ -578,20 +629,21 @@ __global__ __launch_bounds__(kDBlock) void dgc_rec_mask_kernel(const uint32_t* _
 // per element made the 256 MiB DGC step 1.36 ms.)
 // compensate in place (r, a) or, for the world-1 fused step's fix-up, from (r, a) into (ro, ao)
 // (GATED: only when that step's speculative pass flagged meta->fix)
-template <bool GATED>
-__global__ __launch_bounds__(kDBlock) void dgc_compensate_kernel(const float* __restrict__ g, const float* r,
+template <bool GATED, typename GT = float>
+__global__ __launch_bounds__(kDBlock) void dgc_compensate_kernel(const GT* __restrict__ g, const float* r,
                                                                 const float* a, int has_state,
                                                                 float momentum, int64_t n, float* ro, float* ao,
                                                                 const DgcMeta* __restrict__ gate) {
   if constexpr (GATED) { if (gate->fix == 0u) return; }
   const int64_t stride = (int64_t)gridDim.x * kDBlock;
-  const int64_t nq = (al16(g) && al16(r) && al16(a) && al16(ro) && al16(ao)) ? n >> 2 : 0;
+  const int64_t nq = (alq(g) && al16(r) && al16(a) && al16(ro) && al16(ao)) ? n >> 2 : 0;
   for (int64_t q0 = (int64_t)blockIdx.x * kDBlock + threadIdx.x; q0 < nq; q0 += stride * kDQ) {
-    f4d gv[kDQ], rv[kDQ], av[kDQ];
+    typename Quad<GT>::raw gr[kDQ];
+    f4d rv[kDQ], av[kDQ];
 #pragma unroll
     for (int u = 0; u < kDQ; ++u) {
       const int64_t q = q0 + u * stride < nq ? q0 + u * stride : q0;
-      gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f4d*>(g) + q);
+      gr[u] = ldq(g, q);
       if (has_state) {
         rv[u] = __builtin_nontemporal_load(reinterpret_cast<const f4d*>(r) + q);
         av[u] = __builtin_nontemporal_load(reinterpret_cast<const f4d*>(a) + q);
@@ -600,10 +652,11 @@ __global__ __launch_bounds__(kDBlock) void dgc_compensate_kernel(const float* __
 #pragma unroll
     for (int u = 0; u < kDQ; ++u) {
       if (q0 + u * stride >= nq) break;
+      const f4d gv = Quad<GT>::widen(gr[u]);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float rj = has_state ? rv[u][j] : 0.f, aj = has_state ? av[u][j] : 0.f;
-        dgc_comp1(gv[u][j], rj, aj, has_state, momentum);
+        dgc_comp1(gv[j], rj, aj, has_state, momentum);
         rv[u][j] = rj;
         av[u][j] = aj;
       }
@@ -613,7 +666,7 @@ __global__ __launch_bounds__(kDBlock) void dgc_compensate_kernel(const float* __
   }
   for (int64_t i = nq * 4 + (int64_t)blockIdx.x * kDBlock + threadIdx.x; i < n; i += stride) {
     float rv = has_state ? r[i] : 0.f, av = has_state ? a[i] : 0.f;
-    dgc_comp1(g[i], rv, av, has_state, momentum);
+    dgc_comp1(ld1(g, i), rv, av, has_state, momentum);
     ro[i] = rv;
     ao[i] = av;
   }
@@ -628,18 +681,18 @@ __global__ __launch_bounds__(kDBlock) void dgc_compensate_kernel(const float* __
 // the workgroup that arrives last checks the loop's first test on the exact count.  If thr0 does
 // not stand, meta->fix is set and the gated fix-up launches (compensate from the untouched old
 // state, count, replay, mask) redo the step exactly; otherwise they return at once.
-template <bool HAS>
-__global__ __launch_bounds__(kDBlock) void dgc_w1_spec_kernel(const float* __restrict__ g, const float* __restrict__ r,
+template <bool HAS, typename T = float>
+__global__ __launch_bounds__(kDBlock) void dgc_w1_spec_kernel(const T* __restrict__ g, const float* __restrict__ r,
                                                              const float* __restrict__ a, float momentum, int64_t n,
                                                              double ratio, DgcMeta* __restrict__ meta,
                                                              uint32_t* __restrict__ part, float* __restrict__ ro,
-                                                             float* __restrict__ ao, float* __restrict__ out) {
+                                                             float* __restrict__ ao, T* __restrict__ out) {
   __shared__ uint32_t sc[kDBlock / kWave];
   __shared__ uint32_t s_last;
   const float thr = __uint_as_float(meta->thr0);
   const int64_t base = (int64_t)blockIdx.x * kDChunkW1;
   const int64_t end = min(base + (int64_t)kDChunkW1, n);
-  const bool vec = al16(g) && al16(r) && al16(a) && al16(ro) && al16(ao) && al16(out);
+  const bool vec = alq(g) && al16(r) && al16(a) && al16(ro) && al16(ao) && alq(out);
   const int64_t qe = vec ? base + ((end - base) & ~(int64_t)3) : base;
   uint32_t cnt = 0;
   auto one = [&](float gv, float rv, float av, float& rn, float& an, float& o) {
@@ -652,11 +705,12 @@ __global__ __launch_bounds__(kDBlock) void dgc_w1_spec_kernel(const float* __res
     an = av * keep;
   };
   for (int64_t e0 = base + 4 * (int64_t)threadIdx.x; e0 < qe; e0 += 4 * (int64_t)kDBlock * kDQ) {
-    f4d gv[kDQ], rv[kDQ], av[kDQ];
+    typename Quad<T>::raw gr[kDQ];
+    f4d rv[kDQ], av[kDQ];
 #pragma unroll
     for (int u = 0; u < kDQ; ++u) {
       const int64_t e = e0 + 4 * (int64_t)u * kDBlock < qe ? e0 + 4 * (int64_t)u * kDBlock : e0;
-      gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f4d*>(g + e));
+      gr[u] = ldq(g + e);
       if (HAS) {
         rv[u] = __builtin_nontemporal_load(reinterpret_cast<const f4d*>(r + e));
         av[u] = __builtin_nontemporal_load(reinterpret_cast<const f4d*>(a + e));
@@ -666,26 +720,27 @@ __global__ __launch_bounds__(kDBlock) void dgc_w1_spec_kernel(const float* __res
     for (int u = 0; u < kDQ; ++u) {
       const int64_t e = e0 + 4 * (int64_t)u * kDBlock;
       if (e >= qe) break;
+      const f4d gv = Quad<T>::widen(gr[u]);
       f4d rn, an, o;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float x, y, z;
-        one(gv[u][j], HAS ? rv[u][j] : 0.f, HAS ? av[u][j] : 0.f, x, y, z);
+        one(gv[j], HAS ? rv[u][j] : 0.f, HAS ? av[u][j] : 0.f, x, y, z);
         rn[j] = x;
         an[j] = y;
         o[j] = z;
       }
       __builtin_nontemporal_store(rn, reinterpret_cast<f4d*>(ro + e));
       __builtin_nontemporal_store(an, reinterpret_cast<f4d*>(ao + e));
-      __builtin_nontemporal_store(o, reinterpret_cast<f4d*>(out + e));
+      stq(o, out + e);
     }
   }
   for (int64_t i = qe + threadIdx.x; i < end; i += kDBlock) {
     float x, y, z;
-    one(g[i], HAS ? r[i] : 0.f, HAS ? a[i] : 0.f, x, y, z);
+    one(ld1(g, i), HAS ? r[i] : 0.f, HAS ? a[i] : 0.f, x, y, z);
     ro[i] = x;
     ao[i] = y;
-    out[i] = z;
+    st1(out, i, z);
   }
   // the chunk's count, write-through; the last workgroup to arrive decides whether thr0 stands
   cnt = wave_sum(cnt);
@@ -731,14 +786,14 @@ __global__ __launch_bounds__(kDBlock) void dgc_w1_spec_kernel(const float* __res
 // (t is the compensated tensor the mask came from; it may alias a).  OUT: the world-1 Allgather
 // result in the same pass, out = 0 + t where selected and 0 elsewhere -- (0 + decompress) / 1
 // of the payload grace_dgc_write would have produced (dgc.py:45-50, allgather.py:40-45).
-template <bool OUT, bool GATED = false>
+template <bool OUT, bool GATED = false, typename OT = float>
 __global__ __launch_bounds__(kDBlock) void dgc_mask_kernel(const float* t, float* r, float* a, int64_t n,
-                                                          const DgcMeta* __restrict__ meta, float* out) {
+                                                          const DgcMeta* __restrict__ meta, OT* out) {
   if constexpr (GATED) { if (meta->fix == 0u) return; }
   const float thr = __uint_as_float(meta->thr);
   const bool alias = t == a;
   const int64_t stride = (int64_t)gridDim.x * kDBlock;
-  const int64_t nq = (al16(t) && al16(r) && al16(a) && (!OUT || al16(out))) ? n >> 2 : 0;
+  const int64_t nq = (al16(t) && al16(r) && al16(a) && (!OUT || alq(out))) ? n >> 2 : 0;
   for (int64_t q0 = (int64_t)blockIdx.x * kDBlock + threadIdx.x; q0 < nq; q0 += stride * kDQ) {
     f4d tv[kDQ], rv[kDQ], av[kDQ];
 #pragma unroll
@@ -763,7 +818,7 @@ __global__ __launch_bounds__(kDBlock) void dgc_mask_kernel(const float* t, float
       }
       __builtin_nontemporal_store(rv[u], reinterpret_cast<f4d*>(r) + q0 + u * stride);
       __builtin_nontemporal_store(av[u], reinterpret_cast<f4d*>(a) + q0 + u * stride);
-      if constexpr (OUT) __builtin_nontemporal_store(o, reinterpret_cast<f4d*>(out) + q0 + u * stride);
+      if constexpr (OUT) __builtin_nontemporal_store(Quad<OT>::narrow(o), qptr(out) + q0 + u * stride);
     }
   }
   for (int64_t i = nq * 4 + (int64_t)blockIdx.x * kDBlock + threadIdx.x; i < n; i += stride) {
@@ -773,16 +828,17 @@ __global__ __launch_bounds__(kDBlock) void dgc_mask_kernel(const float* t, float
     const float av = alias ? tv : a[i];
     r[i] = r[i] * keep;
     a[i] = av * keep;
-    if constexpr (OUT) out[i] = sel ? 0.f + tv : 0.f;
+    if constexpr (OUT) st1(out, i, sel ? 0.f + tv : 0.f);
   }
 }
 
 // gradient clipping (memory/dgc.py:16-19): sum of squares (f64 accumulate) of one tensor
-__global__ __launch_bounds__(kDBlock) void sumsq_kernel(const float* __restrict__ x, int64_t n,
+template <typename T = float>
+__global__ __launch_bounds__(kDBlock) void sumsq_kernel(const T* __restrict__ x, int64_t n,
                                                        double* __restrict__ part) {
   double s = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * kDBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kDBlock) {
-    const double v = x[i];
+    const double v = ld1(x, i);
     s += v * v;
   }
   s = wave_sum(s);
@@ -808,11 +864,12 @@ __global__ void sumsq_finish_kernel(const double* __restrict__ part, int nb, flo
 // torch.clamp propagates NaN both ways -- a NaN element stays NaN, a NaN bound (a NaN anywhere in the
 // gradient, through s) makes every element NaN -- and leaves the sign of a zero alone; fminf / fmaxf
 // return the other operand for a NaN, so the clamp is spelt out in compares, which a NaN fails.
-__global__ __launch_bounds__(kDBlock) void clip_kernel(const float* __restrict__ x, const float* __restrict__ s,
+template <typename T = float>
+__global__ __launch_bounds__(kDBlock) void clip_kernel(const T* __restrict__ x, const float* __restrict__ s,
                                                       float world, float* __restrict__ out, int64_t n) {
   const float c = sqrtf(*s / world);
   for (int64_t i = (int64_t)blockIdx.x * kDBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kDBlock) {
-    const float v = x[i];
+    const float v = ld1(x, i);
     out[i] = c != c ? c : (v < -c ? -c : (v > c ? c : v));
   }
 }
@@ -820,6 +877,47 @@ __global__ __launch_bounds__(kDBlock) void clip_kernel(const float* __restrict__
 }  // namespace grace
 
 using namespace grace;
+
+// the world-1 fused step for a float or a bfloat16 gradient and dense result (state f32 either way)
+template <typename T>
+static grace_status_t dgc_step_w1_fused_any(const char* name, const char* bad, const char* aliased, const T* g,
+                                            const float* residual, const float* accum, int32_t has_state,
+                                            float momentum, int64_t n, const float* top_vals, int64_t ks, double ratio,
+                                            void* ws, float* residual_out, float* accum_out, T* out, void* stream) {
+  GRACE_REQUIRE(g && top_vals && ws && residual_out && accum_out && out && n >= 1 && ks >= 1 &&
+                    (!has_state || (residual && accum)) && n < ((int64_t)1 << 40),
+                bad);
+  GRACE_REQUIRE(residual_out != residual && accum_out != accum && residual_out != accum_out, aliased);
+  hipStream_t s = as_stream(stream);
+  DgcWs w = dgc_carve(ws, n);
+  uint32_t* part = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws) + dgc_ws_bytes(n) + 256);
+  const int64_t nch = (n + kDChunkW1 - 1) / kDChunkW1;
+  GRACE_REQUIRE(nch < ((int64_t)1 << 31), bad);
+  dgc_thr0_kernel<<<1, 1024, 0, s>>>(top_vals, ks, w);
+  GRACE_CHECK_LAUNCH(name);
+  if (has_state)
+    dgc_w1_spec_kernel<true, T><<<(unsigned)nch, kDBlock, 0, s>>>(g, residual, accum, momentum, n, ratio, w.meta, part,
+                                                                residual_out, accum_out, out);
+  else
+    dgc_w1_spec_kernel<false, T><<<(unsigned)nch, kDBlock, 0, s>>>(g, residual, accum, momentum, n, ratio, w.meta,
+                                                                 part, residual_out, accum_out, out);
+  GRACE_CHECK_LAUNCH(name);
+  // gated fix-up (returns at once unless thr0 did not stand): the reference's full adjustment loop,
+  // on grids small enough that the no-op launches cost little
+  dgc_table_kernel<true><<<1, 1024, 0, s>>>(top_vals, ks, w);   // the adjustment table, zeroed counts
+  GRACE_CHECK_LAUNCH(name);
+  const unsigned sg = stream_grid((n + 3) / 4, kDBlock * kDQ, 1024);
+  dgc_compensate_kernel<true, T><<<sg, kDBlock, 0, s>>>(g, residual, accum, has_state, momentum, n, residual_out,
+                                                        accum_out, w.meta);
+  GRACE_CHECK_LAUNCH(name);
+  dgc_count_kernel<true><<<stream_grid((n + 3) / 4, kDBlock, 1024), kDBlock, 0, s>>>(accum_out, n, w);
+  GRACE_CHECK_LAUNCH(name);
+  dgc_replay_kernel<true><<<1, 64, 0, s>>>(n, ratio, w);
+  GRACE_CHECK_LAUNCH(name);
+  dgc_mask_kernel<true, true, T><<<sg, kDBlock, 0, s>>>(accum_out, residual_out, accum_out, n, w.meta, out);
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
 
 extern "C" {
 
@@ -898,7 +996,7 @@ grace_status_t grace_dgc_mask_update(const float* t, float* residual, float* acc
   GRACE_REQUIRE(t && residual && accum && ws && n >= 0, "grace_dgc_mask_update: bad arguments");
   if (n == 0) return GRACE_OK;
   dgc_mask_kernel<false><<<stream_grid((n + 3) / 4, kDBlock * kDQ, 4096), kDBlock, 0, as_stream(stream)>>>(
-      t, residual, accum, n, reinterpret_cast<const DgcMeta*>(ws), nullptr);
+      t, residual, accum, n, reinterpret_cast<const DgcMeta*>(ws), static_cast<float*>(nullptr));
   GRACE_CHECK_LAUNCH("grace_dgc_mask_update");
   return GRACE_OK;
 }
@@ -964,39 +1062,53 @@ size_t grace_dgc_step_w1_fused_workspace_bytes(int64_t n) {
 grace_status_t grace_dgc_step_w1_fused(const float* g, const float* residual, const float* accum, int32_t has_state,
                                        float momentum, int64_t n, const float* top_vals, int64_t ks, double ratio,
                                        void* ws, float* residual_out, float* accum_out, float* out, void* stream) {
-  GRACE_REQUIRE(g && top_vals && ws && residual_out && accum_out && out && n >= 1 && ks >= 1 &&
-                    (!has_state || (residual && accum)) && n < ((int64_t)1 << 40),
-                "grace_dgc_step_w1_fused: bad arguments");
-  GRACE_REQUIRE(residual_out != residual && accum_out != accum && residual_out != accum_out,
-                "grace_dgc_step_w1_fused: the new state must not alias the old");
-  hipStream_t s = as_stream(stream);
-  DgcWs w = dgc_carve(ws, n);
-  uint32_t* part = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws) + dgc_ws_bytes(n) + 256);
-  const int64_t nch = (n + kDChunkW1 - 1) / kDChunkW1;
-  GRACE_REQUIRE(nch < ((int64_t)1 << 31), "grace_dgc_step_w1_fused: too many chunks");
-  dgc_thr0_kernel<<<1, 1024, 0, s>>>(top_vals, ks, w);
-  GRACE_CHECK_LAUNCH("grace_dgc_step_w1_fused");
-  if (has_state)
-    dgc_w1_spec_kernel<true><<<(unsigned)nch, kDBlock, 0, s>>>(g, residual, accum, momentum, n, ratio, w.meta, part,
-                                                             residual_out, accum_out, out);
-  else
-    dgc_w1_spec_kernel<false><<<(unsigned)nch, kDBlock, 0, s>>>(g, residual, accum, momentum, n, ratio, w.meta, part,
-                                                              residual_out, accum_out, out);
-  GRACE_CHECK_LAUNCH("grace_dgc_step_w1_fused");
-  // gated fix-up (returns at once unless thr0 did not stand): the reference's full adjustment loop,
-  // on grids small enough that the no-op launches cost little
-  dgc_table_kernel<true><<<1, 1024, 0, s>>>(top_vals, ks, w);   // the adjustment table, zeroed counts
-  GRACE_CHECK_LAUNCH("grace_dgc_step_w1_fused");
-  const unsigned sg = stream_grid((n + 3) / 4, kDBlock * kDQ, 1024);
-  dgc_compensate_kernel<true><<<sg, kDBlock, 0, s>>>(g, residual, accum, has_state, momentum, n, residual_out,
-                                                     accum_out, w.meta);
-  GRACE_CHECK_LAUNCH("grace_dgc_step_w1_fused");
-  dgc_count_kernel<true><<<stream_grid((n + 3) / 4, kDBlock, 1024), kDBlock, 0, s>>>(accum_out, n, w);
-  GRACE_CHECK_LAUNCH("grace_dgc_step_w1_fused");
-  dgc_replay_kernel<true><<<1, 64, 0, s>>>(n, ratio, w);
-  GRACE_CHECK_LAUNCH("grace_dgc_step_w1_fused");
-  dgc_mask_kernel<true, true><<<sg, kDBlock, 0, s>>>(accum_out, residual_out, accum_out, n, w.meta, out);
-  GRACE_CHECK_LAUNCH("grace_dgc_step_w1_fused");
+  return dgc_step_w1_fused_any<float>("grace_dgc_step_w1_fused", "grace_dgc_step_w1_fused: bad arguments",
+                                      "grace_dgc_step_w1_fused: the new state must not alias the old", g, residual,
+                                      accum, has_state, momentum, n, top_vals, ks, ratio, ws, residual_out, accum_out,
+                                      out, stream);
+}
+
+grace_status_t grace_dgc_step_w1_fused_bf16(const uint16_t* g, const float* residual, const float* accum,
+                                            int32_t has_state, float momentum, int64_t n, const float* top_vals,
+                                            int64_t ks, double ratio, void* ws, float* residual_out, float* accum_out,
+                                            uint16_t* out, void* stream) {
+  return dgc_step_w1_fused_any<uint16_t>("grace_dgc_step_w1_fused_bf16", "grace_dgc_step_w1_fused_bf16: bad arguments",
+                                         "grace_dgc_step_w1_fused_bf16: the new state must not alias the old", g,
+                                         residual, accum, has_state, momentum, n, top_vals, ks, ratio, ws, residual_out,
+                                         accum_out, out, stream);
+}
+
+grace_status_t grace_dgc_sample_comp_bf16(const uint16_t* g, const float* residual, const float* accum,
+                                          int32_t has_state, float momentum, int64_t n, const int64_t* sample_idx,
+                                          uint64_t seed, int64_t ns, float* sample_abs, void* stream) {
+  GRACE_REQUIRE(g && sample_abs && n >= 1 && ns >= 1 && (!has_state || (residual && accum)),
+                "grace_dgc_sample_comp_bf16: bad arguments");
+  dgc_sample_comp_kernel<uint16_t><<<stream_grid(ns, kDBlock, 1024), kDBlock, 0, as_stream(stream)>>>(
+      g, residual, accum, has_state, momentum, n, sample_idx, seed, ns, sample_abs);
+  GRACE_CHECK_LAUNCH("grace_dgc_sample_comp_bf16");
+  return GRACE_OK;
+}
+
+grace_status_t grace_dgc_compensate_bf16(const uint16_t* g, float* residual, float* accum, int32_t has_state,
+                                         float momentum, int64_t n, void* stream) {
+  GRACE_REQUIRE(g && residual && accum && residual != accum && n >= 0, "grace_dgc_compensate_bf16: bad arguments");
+  if (n == 0) return GRACE_OK;
+  dgc_compensate_kernel<false, uint16_t>
+      <<<stream_grid((n + 3) / 4, kDBlock * kDQ, 4096), kDBlock, 0, as_stream(stream)>>>(
+          g, residual, accum, has_state, momentum, n, residual, accum, nullptr);
+  GRACE_CHECK_LAUNCH("grace_dgc_compensate_bf16");
+  return GRACE_OK;
+}
+
+grace_status_t grace_dgc_step_w1_bf16(const float* t, float* residual, float* accum, int64_t n, const void* ws,
+                                      uint16_t* out, void* stream) {
+  GRACE_REQUIRE(t && residual && accum && residual != accum && ws && out && n >= 0,
+                "grace_dgc_step_w1_bf16: bad arguments");
+  if (n == 0) return GRACE_OK;
+  dgc_mask_kernel<true, false, uint16_t>
+      <<<stream_grid((n + 3) / 4, kDBlock * kDQ, 4096), kDBlock, 0, as_stream(stream)>>>(
+          t, residual, accum, n, reinterpret_cast<const DgcMeta*>(ws), out);
+  GRACE_CHECK_LAUNCH("grace_dgc_step_w1_bf16");
   return GRACE_OK;
 }
 
@@ -1019,6 +1131,26 @@ grace_status_t grace_clip_by_sumsq(const float* x, const float* sumsq_dev, float
   if (n == 0) return GRACE_OK;
   clip_kernel<<<stream_grid(n, kDBlock, 2048), kDBlock, 0, as_stream(stream)>>>(x, sumsq_dev, world, out, n);
   GRACE_CHECK_LAUNCH("grace_clip_by_sumsq");
+  return GRACE_OK;
+}
+
+grace_status_t grace_sumsq_bf16(const uint16_t* x, int64_t n, void* ws, float* out, void* stream) {
+  GRACE_REQUIRE(x && ws && out && n >= 0, "grace_sumsq_bf16: bad arguments");
+  const unsigned nb = n ? stream_grid(n, kDBlock, 1024) : 1;   // grace_sumsq's grid: the same partial sums
+  hipStream_t s = as_stream(stream);
+  sumsq_kernel<uint16_t><<<nb, kDBlock, 0, s>>>(x, n, reinterpret_cast<double*>(ws));
+  GRACE_CHECK_LAUNCH("grace_sumsq_bf16");
+  sumsq_finish_kernel<<<1, 64, 0, s>>>(reinterpret_cast<const double*>(ws), (int)nb, out);
+  GRACE_CHECK_LAUNCH("grace_sumsq_bf16");
+  return GRACE_OK;
+}
+
+grace_status_t grace_clip_by_sumsq_bf16(const uint16_t* x, const float* sumsq_dev, float world, float* out, int64_t n,
+                                        void* stream) {
+  GRACE_REQUIRE(x && sumsq_dev && out && n >= 0 && world > 0.f, "grace_clip_by_sumsq_bf16: bad arguments");
+  if (n == 0) return GRACE_OK;
+  clip_kernel<uint16_t><<<stream_grid(n, kDBlock, 2048), kDBlock, 0, as_stream(stream)>>>(x, sumsq_dev, world, out, n);
+  GRACE_CHECK_LAUNCH("grace_clip_by_sumsq_bf16");
   return GRACE_OK;
 }
 

@@ -839,13 +839,31 @@ def exchange_record_words(cap):
     return int(_lib.query("grace_exchange_record_words", int(cap)))
 
 
-def sparse_aggregate_capped(recs, cap, world, n, divisor, stat):
+RECORDS_BF16_MAX_WORLD = 1024   # records.hip kRMaxRanks
+
+
+def sparse_aggregate_capped(recs, cap, world, n, divisor, stat, out_dtype=F32):
     """Rank-ordered decode+aggregate of W gathered capacity-bounded records (counts read from the
-    record headers on the device); stat (int32[2] on the device) <- {max count, overflow flag}."""
+    record headers on the device); stat (int32[2] on the device) <- {max count, overflow flag}.
+    out_dtype=torch.bfloat16: the same sum and division rounded once to bf16, written tile by tile in
+    one pass over the output (grace_sparse_aggregate_records_bf16; the records' indices must ascend
+    within a rank, n < 2^31, world <= 1024)."""
+    out_dtype = _dense_dtype(out_dtype, "sparse_aggregate_capped")
     require_dev(recs, "records")
     stride = exchange_record_words(cap)
     if recs.numel() != world * stride or recs.dtype != torch.int32 or stat.numel() < 2:
         raise ValueError("sparse_aggregate_capped: records / stat do not match (world, cap)")
+    if out_dtype == BF16:
+        world, cap, n = int(world), int(cap), int(n)
+        if not (1 <= cap <= n < 2 ** 31 and 1 <= world <= RECORDS_BF16_MAX_WORLD):
+            raise ValueError("grace_amd: sparse_aggregate_capped: a bfloat16 result needs 1 <= cap <= n < 2^31 and "
+                             f"1 <= world <= {RECORDS_BF16_MAX_WORLD}, got cap={cap}, n={n}, world={world}")
+        out = torch.empty(n, dtype=BF16, device=recs.device)
+        nbytes = _lib.query("grace_sparse_aggregate_records_bf16_workspace_bytes", world, n)
+        ws = workspace("records_bf16", nbytes, recs.device)
+        _lib.call("grace_sparse_aggregate_records_bf16", _p(recs), stride, cap, world, float(divisor), _p(out), n,
+                  _p(stat), _p(ws), nbytes, _stream())
+        return out
     out = torch.empty(n, dtype=F32, device=recs.device)
     _lib.call("grace_sparse_aggregate_capped", _p(recs), stride, int(cap), int(world), float(divisor), _p(out),
               _p(_agg_tags(recs.device, n)), int(n), _p(stat), _stream())
@@ -1581,13 +1599,22 @@ def dgc_sample(t, ns, sample_idx=None, seed=0):
     return sample
 
 
+def _dgc_bf16_state(g, residual, accum, has_state, what):
+    """The memory a bfloat16 gradient steps against is the f32 class's: contiguous f32, g's length."""
+    if g.dtype == BF16 and has_state and not (_f32_residual(residual, g.numel(), g.device)
+                                              and _f32_residual(accum, g.numel(), g.device)):
+        raise TypeError(f"grace_amd: {what}: the residual and accumulator of a bfloat16 gradient must be contiguous "
+                        f"float32 tensors of {g.numel()} elements on {g.device}")
+
+
 def dgc_sample_comp(g, residual, accum, has_state, momentum, ns, sample_idx=None, seed=0):
     """dgc_sample of the tensor DgcMemory.compensate would make of gradient g and the memory
     (residual, accum) -- g itself without state -- read from the state BEFORE compensation
-    (grace_dgc_sample_comp)."""
-    g = dev_f32(g)
+    (grace_dgc_sample_comp).  g is f32 or bf16 (widened exactly); the state is f32 either way."""
+    g = dev_grad(g)
+    _dgc_bf16_state(g, residual, accum, has_state, "dgc_sample_comp")
     sample = torch.empty(ns, dtype=F32, device=g.device)
-    _lib.call("grace_dgc_sample_comp", _p(g), _p(residual) if has_state else None,
+    _lib.call(_entry("grace_dgc_sample_comp", g.dtype), _p(g), _p(residual) if has_state else None,
               _p(accum) if has_state else None, 1 if has_state else 0, float(momentum), g.numel(), _p(sample_idx),
               seed64(seed), ns, _p(sample), _stream())
     return sample
@@ -1659,30 +1686,44 @@ def dgc_select(t, ratio, sample_idx=None, seed=0):
     return _dgc_threshold(dev_f32(t), ratio, sample_idx, seed, "grace_dgc_select")
 
 
-def dgc_step_w1(t, residual, accum, ws, out=None):
+def dgc_step_w1(t, residual, accum, ws, out=None, out_dtype=F32):
+    """Mask the memory at ws's final threshold and write the world-1 result 0 + t | 0 in out_dtype
+    (float32, or bfloat16: rounded once, grace_dgc_step_w1_bf16); t, residual and accum are f32."""
+    out_dtype = _dense_dtype(out_dtype, "dgc_step_w1")
     t = dev_f32(t)
-    out = torch.empty_like(t) if out is None else out
-    _lib.call("grace_dgc_step_w1", _p(t), _p(residual), _p(accum), t.numel(), _p(ws), _p(out), _stream())
+    if out_dtype == BF16:
+        out = _bf16_out(out, t.numel(), t.device, "dgc_step_w1")
+    else:
+        out = torch.empty_like(t) if out is None else out
+    _lib.call(_entry("grace_dgc_step_w1", out_dtype), _p(t), _p(residual), _p(accum), t.numel(), _p(ws), _p(out),
+              _stream())
     return out
 
 
 def dgc_step_w1_fused(g, residual, accum, has_state, momentum, ratio, sample_idx=None, seed=0):
     """World-1 Allgather(DGC, DgcMemory).step from the OLD memory state (grace_dgc_sample_comp +
     grace_dgc_step_w1_fused): returns (out, new residual, new accumulator); the old buffers are only
-    read.  Same values as compensate + select + step_w1."""
-    g = dev_f32(g)
+    read.  Same values as compensate + select + step_w1.  A bfloat16 g is read as it is
+    (grace_dgc_step_w1_fused_bf16): the new state is f32 and bit for bit the f32 step's for g.float(),
+    out is bf16, that step's out rounded once."""
+    g = dev_grad(g)
+    _dgc_bf16_state(g, residual, accum, has_state, "dgc_step_w1_fused")
     n = g.numel()
     top, kt = _dgc_sample_top_of(g, ratio, sample_idx, seed, state=(residual, accum, has_state, momentum))
     ws = workspace("dgc_w1", _lib.query("grace_dgc_step_w1_fused_workspace_bytes", n), g.device)
-    r_new, a_new, out = torch.empty_like(g), torch.empty_like(g), torch.empty_like(g)
-    _lib.call("grace_dgc_step_w1_fused", _p(g), _p(residual) if has_state else None,
+    r_new, a_new = torch.empty(n, dtype=F32, device=g.device), torch.empty(n, dtype=F32, device=g.device)
+    out = torch.empty_like(g)
+    _lib.call(_entry("grace_dgc_step_w1_fused", g.dtype), _p(g), _p(residual) if has_state else None,
               _p(accum) if has_state else None, 1 if has_state else 0, float(momentum), n, _p(top), kt,
               float(ratio), _p(ws), _p(r_new), _p(a_new), _p(out), _stream())
     return out, r_new, a_new
 
 
 def dgc_compensate(g, residual, accum, has_state, momentum):
-    _lib.call("grace_dgc_compensate", _p(dev_f32(g)), _p(residual), _p(accum), 1 if has_state else 0,
+    """r = m r + g, a = a + r in place (first step r = a = g); g is f32 or bf16, r and a f32."""
+    g = dev_grad(g)
+    _dgc_bf16_state(g, residual, accum, True, "dgc_compensate")   # written in place on a first step too
+    _lib.call(_entry("grace_dgc_compensate", g.dtype), _p(g), _p(residual), _p(accum), 1 if has_state else 0,
               float(momentum), g.numel(), _stream())
 
 
@@ -1691,20 +1732,22 @@ def dgc_mask_update(t, residual, accum, meta):
 
 
 def sumsq(x):
-    x = dev_f32(x)
+    """(1,) f32 sum of squares; a bf16 x gives bit for bit sumsq(x.float())."""
+    x = dev_grad(x, "tensor")
     out = torch.empty(1, dtype=F32, device=x.device)
     ws = workspace("sumsq", _lib.query("grace_sumsq_workspace_bytes"), x.device)
-    _lib.call("grace_sumsq", _p(x), x.numel(), _p(ws), _p(out), _stream())
+    _lib.call(_entry("grace_sumsq", x.dtype), _p(x), x.numel(), _p(ws), _p(out), _stream())
     return out
 
 
 def clip_by_sumsq(x, s, world):
     """DgcMemory's gradient clipping: ``x.clamp(-c, c)`` with ``c = sqrt(s / world)``, s the (all-reduced)
     sum of squares on the device.  torch.clamp's NaN rule: a NaN element stays NaN, and a NaN s -- a NaN
-    anywhere in any rank's gradient -- makes every element NaN, so a diverged step is never made finite."""
-    x = dev_f32(x)
-    out = torch.empty_like(x)
-    _lib.call("grace_clip_by_sumsq", _p(x), _p(s), float(world), _p(out), x.numel(), _stream())
+    anywhere in any rank's gradient -- makes every element NaN, so a diverged step is never made finite.
+    x is f32 or bf16; the result is f32 either way (the bound is not a bfloat16 number)."""
+    x = dev_grad(x, "tensor")
+    out = torch.empty(x.numel(), dtype=F32, device=x.device)
+    _lib.call(_entry("grace_clip_by_sumsq", x.dtype), _p(x), _p(s), float(world), _p(out), x.numel(), _stream())
     return out
 
 

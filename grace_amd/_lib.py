@@ -1,5 +1,6 @@
 """ctypes binding of libgrace_hip.so (the C ABI declared in include/grace_hip.h,
-include/grace_hip_sign.h, include/grace_hip_quant.h and include/grace_hip_dgc.h).
+include/grace_hip_sign.h, include/grace_hip_quant.h, include/grace_hip_dgc.h and
+include/grace_hip_sparse.h).
 
 The library is the only compute path of grace_amd: there is no CPU or eager-PyTorch fallback.
 If the shared object is missing (not built) or a tensor is not on the GPU, calls raise.
@@ -225,6 +226,19 @@ SIGNATURES_DGC = {
     "grace_sparse_aggregate_records_bf16": (ST, [P, I64, I64, I32, F32, P, I64, P, P, SZ, P]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/grace_hip_sparse.h (threshold and
+# random-k on bfloat16: the twins have their f32 forms' argument lists, the recycled output's two
+# grouping buffers dropped from the dense random-k step; the padded decode writes a bf16 dense result)
+SIGNATURES_SPARSE = {
+    "grace_threshold_step_w1_bf16": SIGNATURES["grace_threshold_step_w1"],
+    "grace_axpby_bf16": (ST, [P, P, I32, F32, F32, P, I64, P]),
+    "grace_randomk_step_w1_dense_bf16": (ST, [P, P, I32, F32, F32, I64, P, I64, P, P, SZ, P]),
+    "grace_randomk_clear": (ST, [P, P, I64, P, I64, P]),
+    "grace_randomk_aggregate_bf16": (ST, [P, P, I64, I32, F32, P, I64, P]),
+    "grace_sparse_aggregate_padded_bf16_workspace_bytes": (SZ, [I32, I64]),
+    "grace_sparse_aggregate_padded_bf16": (ST, [P, I64, P, I32, F32, P, I64, P, SZ, P]),
+}
+
 
 class GraceNativeError(RuntimeError):
     """A native call failed or the native library is unavailable."""
@@ -235,10 +249,10 @@ _lib = None
 
 
 def _bind(lib, strict):
-    """Give every symbol of the four tables its restype and argtypes and return `lib`.  strict: a
+    """Give every symbol of the five tables its restype and argtypes and return `lib`.  strict: a
     symbol the library lacks raises AttributeError; otherwise it stays unbound."""
     for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items(), *SIGNATURES_QUANT.items(),
-                              *SIGNATURES_DGC.items()):
+                              *SIGNATURES_DGC.items(), *SIGNATURES_SPARSE.items()):
         f = getattr(lib, name) if strict else getattr(lib, name, None)
         if f is not None:
             f.restype = res

@@ -1,5 +1,7 @@
 // Rank-ordered aggregate of capacity-bounded exchange records as a bfloat16 dense result (the
-// world > 1 decode of Allgather(DgcCompressor) on a bfloat16 gradient).
+// world > 1 decode of Allgather(DgcCompressor) on a bfloat16 gradient), and of the
+// padded buffers of the threshold counts exchange (grace_sparse_aggregate_padded_bf16):
+// the same two kernels, told where a rank's count, values and indices are by a RecSrc.
 //
 // The f32 decode of sparse.hip (grace_sparse_aggregate_capped) fills the n-element output, scatters
 // one rank per launch with an n-element tag array beside it, and divides in a last launch; a bf16
@@ -23,6 +25,7 @@
 // outside the chunk it was filed under is skipped, and positions past min(count, cap) are not read.
 #include "common.h"
 #include "../../include/grace_hip_dgc.h"
+#include "../../include/grace_hip_sparse.h"
 
 namespace grace {
 
@@ -34,18 +37,38 @@ constexpr int kRMaxRanks = 1024;           // = payload.hip kMaxRanks, the sorte
 constexpr int kRBatch = 8;                 // ranks whose entry loads are in flight together
 constexpr int kRLane = 8;                  // bf16 results per lane per store: 16 B
 
+// Where rank w's count, values and indices are: the capacity-bounded records ({count, cap, 0, 0 | vals
+// f32[cap] | idx i32[cap]}, hdr = 4, counts null: the count is the header's first word), or the padded
+// buffers of the threshold counts exchange ({vals f32[cap] | idx i32[cap]}, hdr = 0, the counts in a
+// device int32[world] array beside them; grace_sparse_aggregate_padded_bf16).  Both kernels below
+// read a rank through this and nothing else.
+struct RecSrc {
+  const uint32_t* base;
+  int64_t stride;          // words between two ranks
+  int64_t cap;
+  const int32_t* counts;   // null: the record header holds the count
+  int hdr;                 // header words in front of vals
+  __device__ __forceinline__ int64_t count(int w) const {   // entries that may be read: in [0, cap]
+    const int64_t c = counts ? (int64_t)max(counts[w], 0) : (int64_t)base[(int64_t)w * stride];
+    return min(c, cap);
+  }
+  __device__ __forceinline__ const float* vals(int w) const {
+    return reinterpret_cast<const float*>(base + (int64_t)w * stride + hdr);
+  }
+  __device__ __forceinline__ const int32_t* idx(int w) const {
+    return reinterpret_cast<const int32_t*>(base + (int64_t)w * stride + hdr + cap);
+  }
+};
+
 __device__ __forceinline__ int rec_chunk_of(int32_t i, int nchunks) {
   const uint32_t c = (uint32_t)i >> kRChunkLog;   // a negative index lands past every chunk
   return c < (uint32_t)nchunks ? (int)c : nchunks;
 }
 
 // bounds[w][c] = the first position of rank w whose index is in chunk c or later, c in [0, nchunks]
-__global__ __launch_bounds__(kRBlock) void rec_bounds_kernel(const uint32_t* __restrict__ recs, int64_t stride,
-                                                            int64_t cap, int nchunks,
-                                                            int32_t* __restrict__ bounds) {
-  const uint32_t* rec = recs + (int64_t)blockIdx.y * stride;
-  const int64_t cnt = min((int64_t)rec[0], cap);
-  const int32_t* idx = reinterpret_cast<const int32_t*>(rec + kRHdr + cap);
+__global__ __launch_bounds__(kRBlock) void rec_bounds_kernel(RecSrc src, int nchunks, int32_t* __restrict__ bounds) {
+  const int64_t cnt = src.count(blockIdx.y);
+  const int32_t* __restrict__ idx = src.idx(blockIdx.y);
   int32_t* bw = bounds + (int64_t)blockIdx.y * (nchunks + 1);
   for (int64_t p = (int64_t)blockIdx.x * kRBlock + threadIdx.x; p <= cnt; p += (int64_t)gridDim.x * kRBlock) {
     const int lo = p == 0 ? -1 : rec_chunk_of(idx[p - 1], nchunks);
@@ -58,9 +81,7 @@ __global__ __launch_bounds__(kRBlock) void rec_bounds_kernel(const uint32_t* __r
 // is the workgroup's only LDS (payload.hip chunk_accumulate_kernel's arrangement: 32 KB, five
 // workgroups per CU instead of four with the 8 KB table beside it).
 template <bool SMALLW>
-__global__ __launch_bounds__(kRBlock) void rec_accumulate_bf16_kernel(const uint32_t* __restrict__ recs,
-                                                                     int64_t stride, int64_t cap,
-                                                                     const int32_t* __restrict__ bounds,
+__global__ __launch_bounds__(kRBlock) void rec_accumulate_bf16_kernel(RecSrc src, const int32_t* __restrict__ bounds,
                                                                      int nchunks, int world, float divisor,
                                                                      uint16_t* __restrict__ out, int64_t n,
                                                                      uint32_t* __restrict__ stat) {
@@ -98,11 +119,11 @@ __global__ __launch_bounds__(kRBlock) void rec_accumulate_bf16_kernel(const uint
     const int64_t li = (int64_t)i - c0;
     return (li >= 0 && li < kRChunk && (int64_t)i < n) ? (int32_t)li : -1;
   };
-  if (ch == 0 && t == 0) {   // grace_sparse_aggregate_capped's stat, identical on every rank
+  if (stat && ch == 0 && t == 0) {   // grace_sparse_aggregate_capped's stat (records only), identical on every rank
     uint32_t mx = 0u;
-    for (int w = 0; w < world; ++w) mx = max(mx, recs[(int64_t)w * stride]);
+    for (int w = 0; w < world; ++w) mx = max(mx, src.base[(int64_t)w * src.stride]);
     stat[0] = mx;
-    stat[1] = (int64_t)mx > cap ? 1u : 0u;
+    stat[1] = (int64_t)mx > src.cap ? 1u : 0u;
   }
   for (int e = t; e < kRChunk; e += kRBlock) tile[e] = 0.f;
   __syncthreads();
@@ -116,9 +137,8 @@ __global__ __launch_bounds__(kRBlock) void rec_accumulate_bf16_kernel(const uint
       bnd(w, b, e);
       const int64_t p = (int64_t)b + t;   // 64-bit: b + t may pass 2^31
       const bool ok = w0 + q < world && p < e;
-      const uint32_t* rec = recs + (int64_t)w * stride + kRHdr;
-      v[q] = reinterpret_cast<const float*>(rec)[ok ? p : 0];   // position 0 exists (cap >= 1), its value unused
-      const int32_t i = reinterpret_cast<const int32_t*>(rec + cap)[ok ? p : 0];
+      v[q] = src.vals(w)[ok ? p : 0];   // position 0 exists (cap >= 1), its value unused
+      const int32_t i = src.idx(w)[ok ? p : 0];
       l[q] = ok ? local(i) : -1;
     }
 #pragma unroll
@@ -130,10 +150,11 @@ __global__ __launch_bounds__(kRBlock) void rec_accumulate_bf16_kernel(const uint
       bnd(w, s0, s1);
       // a rank with more than a block-width of entries here finishes its rounds before the next rank
       // (indices are unique within a rank, so its own rounds need no barrier between them)
-      const uint32_t* rec = recs + (int64_t)w * stride + kRHdr;
+      const float* __restrict__ wv = src.vals(w);
+      const int32_t* __restrict__ wi = src.idx(w);
       for (int64_t p = (int64_t)s0 + kRBlock + t; p < s1; p += kRBlock) {
-        const int32_t lp = local(reinterpret_cast<const int32_t*>(rec + cap)[p]);
-        if (lp >= 0) tile[lp] = tile[lp] + reinterpret_cast<const float*>(rec)[p];
+        const int32_t lp = local(wi[p]);
+        if (lp >= 0) tile[lp] = tile[lp] + wv[p];
       }
       __syncthreads();
     }
@@ -173,6 +194,24 @@ size_t grace_sparse_aggregate_records_bf16_workspace_bytes(int32_t world, int64_
   return rec_bounds_bytes(world, n);
 }
 
+// the boundary pass and the tile decode over either layout
+static grace_status_t rec_decode_bf16(const char* name, const RecSrc& src, int32_t world, float divisor, uint16_t* out,
+                                      int64_t n, uint32_t* stat, void* ws, hipStream_t s) {
+  const int nchunks = (int)((n + kRChunk - 1) / kRChunk);
+  int32_t* bounds = reinterpret_cast<int32_t*>(ws);
+  rec_bounds_kernel<<<dim3(stream_grid(src.cap + 1, kRBlock, 1024), (unsigned)world), kRBlock, 0, s>>>(src, nchunks,
+                                                                                                     bounds);
+  GRACE_CHECK_LAUNCH(name);
+  if (world <= kWave)
+    rec_accumulate_bf16_kernel<true><<<(unsigned)nchunks, kRBlock, 0, s>>>(src, bounds, nchunks, world, divisor, out, n,
+                                                                          stat);
+  else
+    rec_accumulate_bf16_kernel<false><<<(unsigned)nchunks, kRBlock, 0, s>>>(src, bounds, nchunks, world, divisor, out, n,
+                                                                           stat);
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
+
 grace_status_t grace_sparse_aggregate_records_bf16(const uint32_t* recs, int64_t stride, int64_t cap, int32_t world,
                                                    float divisor, uint16_t* out, int64_t n, uint32_t* stat, void* ws,
                                                    size_t ws_bytes, void* stream) {
@@ -181,20 +220,23 @@ grace_status_t grace_sparse_aggregate_records_bf16(const uint32_t* recs, int64_t
                 "grace_sparse_aggregate_records_bf16: bad arguments (1 <= cap <= n < 2^31, 1 <= world <= 1024, "
                 "stride = 4 + 2 cap)");
   GRACE_REQUIRE(ws_bytes >= rec_bounds_bytes(world, n), "grace_sparse_aggregate_records_bf16: workspace too small");
-  hipStream_t s = as_stream(stream);
-  const int nchunks = (int)((n + kRChunk - 1) / kRChunk);
-  int32_t* bounds = reinterpret_cast<int32_t*>(ws);
-  rec_bounds_kernel<<<dim3(stream_grid(cap + 1, kRBlock, 1024), (unsigned)world), kRBlock, 0, s>>>(recs, stride, cap,
-                                                                                                 nchunks, bounds);
-  GRACE_CHECK_LAUNCH("grace_sparse_aggregate_records_bf16");
-  if (world <= kWave)
-    rec_accumulate_bf16_kernel<true><<<(unsigned)nchunks, kRBlock, 0, s>>>(recs, stride, cap, bounds, nchunks, world,
-                                                                          divisor, out, n, stat);
-  else
-    rec_accumulate_bf16_kernel<false><<<(unsigned)nchunks, kRBlock, 0, s>>>(recs, stride, cap, bounds, nchunks, world,
-                                                                           divisor, out, n, stat);
-  GRACE_CHECK_LAUNCH("grace_sparse_aggregate_records_bf16");
-  return GRACE_OK;
+  return rec_decode_bf16("grace_sparse_aggregate_records_bf16", RecSrc{recs, stride, cap, nullptr, kRHdr}, world, divisor,
+                         out, n, stat, ws, as_stream(stream));
+}
+
+size_t grace_sparse_aggregate_padded_bf16_workspace_bytes(int32_t world, int64_t n) {
+  return grace_sparse_aggregate_records_bf16_workspace_bytes(world, n);
+}
+
+grace_status_t grace_sparse_aggregate_padded_bf16(const uint32_t* base, int64_t cap, const int32_t* counts,
+                                                  int32_t world, float divisor, uint16_t* out, int64_t n, void* ws,
+                                                  size_t ws_bytes, void* stream) {
+  GRACE_REQUIRE(base && counts && out && ws && world >= 1 && world <= kRMaxRanks && cap >= 1 && cap <= n &&
+                    n < ((int64_t)1 << 31),
+                "grace_sparse_aggregate_padded_bf16: bad arguments (1 <= cap <= n < 2^31, 1 <= world <= 1024)");
+  GRACE_REQUIRE(ws_bytes >= rec_bounds_bytes(world, n), "grace_sparse_aggregate_padded_bf16: workspace too small");
+  return rec_decode_bf16("grace_sparse_aggregate_padded_bf16", RecSrc{base, 2 * cap, cap, counts, 0}, world, divisor, out,
+                         n, nullptr, ws, as_stream(stream));
 }
 
 }  // extern "C"

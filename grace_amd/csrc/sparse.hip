@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "../../include/grace_hip_sparse.h"
 
 namespace grace {
 
@@ -101,6 +102,52 @@ __global__ __launch_bounds__(kSBlock) void randomk_shard_scatter_kernel(const in
   }
 }
 
+// A gradient and a dense result are float, or bfloat16 as 16-bit patterns (uint16_t), widened exactly
+// and rounded once (common.h f32_to_bf16).  A lane's unit in the streaming passes below:
+//   f32                 one quad of g, of r and of out, 16 B each;
+//   bf16 beside r       the same four elements: 8 B of g and of out beside the 16-B quad of r, so that
+//                       the r stream stays one coalesced quad per lane (dgc.hip's Quad<T>; a lane owning
+//                       eight contiguous elements, 16 B of g beside TWO quads of r, lost there, §12);
+//   bf16 without r      (WIDE; threshold without memory) eight elements: 16 B of g, 16 B of out.
+typedef float f4s __attribute__((ext_vector_type(4)));
+typedef uint32_t u4s __attribute__((ext_vector_type(4)));
+typedef uint32_t u2s __attribute__((ext_vector_type(2)));
+
+template <typename GT, bool WIDE> struct GradIo;
+template <bool WIDE> struct GradIo<float, WIDE> {
+  typedef f4s vec;
+  static constexpr int EL = 4;   // elements per unit
+  static constexpr int U = 4;    // units per lane per round of the threshold pass (all loads first)
+  static __device__ __forceinline__ float widen(float x) { return x; }
+  static __device__ __forceinline__ float narrow(float x) { return x; }
+  static __device__ __forceinline__ float at(const vec& v, int j) { return v[j]; }
+  static __device__ __forceinline__ vec pack(const float (&o)[4]) { return vec{o[0], o[1], o[2], o[3]}; }
+};
+struct GradIoBf16 {
+  static __device__ __forceinline__ float widen(uint16_t x) { return bf16_to_f32(x); }
+  static __device__ __forceinline__ uint16_t narrow(float x) { return f32_to_bf16(x); }
+  template <typename V>
+  static __device__ __forceinline__ float at(const V& v, int j) {   // element 2i in the low half of word i
+    return u2f((j & 1) ? (v[j >> 1] & 0xFFFF0000u) : (v[j >> 1] << 16));
+  }
+};
+template <> struct GradIo<uint16_t, false> : GradIoBf16 {
+  typedef u2s vec;
+  static constexpr int EL = 4;
+  static constexpr int U = 4;
+  static __device__ __forceinline__ vec pack(const float (&o)[4]) {
+    return vec{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
+  }
+};
+template <> struct GradIo<uint16_t, true> : GradIoBf16 {
+  typedef u4s vec;
+  static constexpr int EL = 8;
+  static constexpr int U = 2;    // 2 x 16 B of g per round: the f32 form's 4096 elements
+  static __device__ __forceinline__ vec pack(const float (&o)[8]) {
+    return vec{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7])};
+  }
+};
+
 // World-1 Allgather(RandomK, ResidualMemory).step in ONE streaming pass (the dense variant; no
 // payload is materialised: at world 1 the step's result is out alone).  The drawn indices are
 // grouped by 8192-element chunk first (payload.hip's counting sort: u16 offsets + chunk ends);
@@ -126,7 +173,7 @@ __global__ __launch_bounds__(kSBlock) void randomk_dense_pass_kernel(const float
                                                                     float* __restrict__ out,
                                                                     const uint16_t* __restrict__ poffs,
                                                                     const uint32_t* __restrict__ pends) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
+  typedef f4s f4;
   __shared__ uint32_t bm[kRkChunk / 32];
   const int64_t c = blockIdx.x;
   const int64_t c0 = c << kRkChunkLog, c1 = min(c0 + (int64_t)kRkChunk, n);
@@ -197,6 +244,86 @@ __global__ __launch_bounds__(kSBlock) void randomk_dense_pass_kernel(const float
   }
 }
 
+// The same pass on a bfloat16 g and out, SPARSE = false (grace_randomk_step_w1_dense_bf16; r and r' f32
+// as ever): the same grouping, bitmap and selection, and the f32 kernel's unit -- a lane's four
+// elements are 8 B of g and of out beside the quad of r.  The vector path needs g, r and out 16-byte
+// aligned and a whole chunk; anything else is the scalar loop.  (Its own kernel and not an
+// instantiation of the one above: templating that one on the element type cost its recycled f32 form
+// a wave of occupancy, 95 -> 104 VGPRs.)
+template <bool HAS_RES>
+__global__ __launch_bounds__(kSBlock) void randomk_dense_pass_bf16_kernel(const uint16_t* __restrict__ g,
+                                                                         float* __restrict__ r, float beta, float gamma,
+                                                                         int64_t n, const uint16_t* __restrict__ offs,
+                                                                         const uint32_t* __restrict__ ends,
+                                                                         uint16_t* __restrict__ out) {
+  typedef GradIo<uint16_t, false> Io;
+  constexpr int EL = Io::EL, RQ = EL / 4;
+  constexpr int NU = kRkChunk / (EL * kSBlock);   // units per thread
+  __shared__ uint32_t bm[kRkChunk / 32];
+  const int64_t c = blockIdx.x;
+  const int64_t c0 = c << kRkChunkLog, c1 = min(c0 + (int64_t)kRkChunk, n);
+  const int t = threadIdx.x;
+  const bool vec = ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(r) |
+                     reinterpret_cast<uintptr_t>(out)) & 15u) == 0 && c1 - c0 == kRkChunk;
+  u2s gv[NU];
+  f4s rv[NU][RQ];
+  if (vec) {
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const int64_t e = c0 + EL * ((int64_t)u * kSBlock + t);
+      gv[u] = __builtin_nontemporal_load(reinterpret_cast<const u2s*>(g + e));
+      if (HAS_RES) {
+#pragma unroll
+        for (int h = 0; h < RQ; ++h) rv[u][h] = __builtin_nontemporal_load(reinterpret_cast<const f4s*>(r + e) + h);
+      }
+    }
+  }
+  for (int w = t; w < kRkChunk / 32; w += kSBlock) bm[w] = 0u;
+  __syncthreads();
+  const uint32_t e0 = c > 0 ? ends[c - 1] : 0u, e1 = ends[c];
+  for (uint32_t j = e0 + t; j < e1; j += kSBlock) {
+    const uint32_t o = offs[j];
+    atomicOr(&bm[o >> 5], 1u << (o & 31));
+  }
+  __syncthreads();
+  auto one = [&](float tv, int64_t i, float& o, float& rr) {
+    const int64_t l = i - c0;
+    const bool sel = (bm[l >> 5] >> (l & 31)) & 1u;
+    o = sel ? 0.f + tv : 0.f;
+    rr = sel ? tv - tv : tv;
+  };
+  if (vec) {
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const int64_t e = c0 + EL * ((int64_t)u * kSBlock + t);
+      float o[EL];
+      f4s rr[RQ];
+#pragma unroll
+      for (int j = 0; j < EL; ++j) {
+        const float gj = Io::at(gv[u], j);
+        float tt = gj;
+        if (HAS_RES) tt = beta * rv[u][j >> 2][j & 3] + gamma * gj;
+        float a, b;
+        one(tt, e + j, a, b);
+        o[j] = a;
+        rr[j >> 2][j & 3] = b;
+      }
+      __builtin_nontemporal_store(Io::pack(o), reinterpret_cast<u2s*>(out + e));
+#pragma unroll
+      for (int h = 0; h < RQ; ++h) __builtin_nontemporal_store(rr[h], reinterpret_cast<f4s*>(r + e) + h);
+    }
+  } else {
+    for (int64_t i = c0 + t; i < c1; i += kSBlock) {
+      const float gi = bf16_to_f32(g[i]);
+      const float tv = HAS_RES ? beta * r[i] + gamma * gi : gi;
+      float a, b;
+      one(tv, i, a, b);
+      out[i] = f32_to_bf16(a);
+      r[i] = b;
+    }
+  }
+}
+
 __global__ __launch_bounds__(kSBlock) void randomk_scatter_kernel(const int64_t* __restrict__ idx,
                                                                  const float* __restrict__ vals, int64_t k,
                                                                  float* __restrict__ r, float* __restrict__ out) {
@@ -205,6 +332,47 @@ __global__ __launch_bounds__(kSBlock) void randomk_scatter_kernel(const int64_t*
     const float v = vals[j];
     out[i] = 0.f + v;
     r[i] = v - v;
+  }
+}
+
+// the world > 1 decode of a bfloat16 random-k step (grace_randomk_aggregate_bf16)
+__global__ __launch_bounds__(kSBlock) void randomk_aggregate_bf16_kernel(const float* __restrict__ vals,
+                                                                        const int64_t* __restrict__ idx, int64_t k,
+                                                                        int world, float divisor,
+                                                                        uint16_t* __restrict__ out, int64_t n) {
+  for (int64_t j = (int64_t)blockIdx.x * kSBlock + threadIdx.x; j < k; j += (int64_t)gridDim.x * kSBlock) {
+    const int64_t i = idx[j];
+    if (i < 0 || i >= n) continue;
+    float acc = 0.f;
+    for (int w = 0; w < world; ++w) acc = acc + vals[(int64_t)w * k + j];
+    out[i] = f32_to_bf16(divisor != 1.0f ? acc / divisor : acc);
+  }
+}
+
+// t = beta r + gamma widen(g) (grace_axpby_bf16), grace_axpby's streaming shape: a lane's unit is four
+// elements, 8 B of g beside 16 B of r and of t, which needs g 8-byte and r, t 16-byte aligned; anything
+// else is the scalar loop.  r and t may be the same buffer (each element is read before it is written).
+template <bool HAS_RES>
+__global__ __launch_bounds__(kSBlock) void axpby_bf16_kernel(const float* r, const uint16_t* __restrict__ g, float beta,
+                                                            float gamma, float* t, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * kSBlock, gid = (int64_t)blockIdx.x * kSBlock + threadIdx.x;
+  const bool vec = ((reinterpret_cast<uintptr_t>(g) & 7u) | ((HAS_RES ? reinterpret_cast<uintptr_t>(r) : 0u) & 15u) |
+                    (reinterpret_cast<uintptr_t>(t) & 15u)) == 0;
+  const int64_t n4 = vec ? n >> 2 : 0;
+  for (int64_t i = gid; i < n4; i += stride) {
+    const uint2 b = reinterpret_cast<const uint2*>(g)[i];
+    const float4 w = make_float4(u2f(b.x << 16), u2f(b.x & 0xFFFF0000u), u2f(b.y << 16), u2f(b.y & 0xFFFF0000u));
+    float4 o = w;
+    if (HAS_RES) {
+      const float4 a = reinterpret_cast<const float4*>(r)[i];
+      o.x = beta * a.x + gamma * w.x; o.y = beta * a.y + gamma * w.y;
+      o.z = beta * a.z + gamma * w.z; o.w = beta * a.w + gamma * w.w;
+    }
+    reinterpret_cast<float4*>(t)[i] = o;
+  }
+  for (int64_t i = (n4 << 2) + gid; i < n; i += stride) {
+    const float w = bf16_to_f32(g[i]);
+    t[i] = HAS_RES ? beta * r[i] + gamma * w : w;
   }
 }
 
@@ -308,20 +476,29 @@ __global__ __launch_bounds__(kSBlock) void thr_stats_kernel(const float* __restr
 // fix-up kernel returns at once when nothing needs fixing.  Two launches and one read of the
 // inputs in the common case, against three launches and t written then re-read before.
 // MODE 0: no memory (t = g, read-only); 1: residual memory, first step (t = g); 2: residual memory.
-typedef float f4s __attribute__((ext_vector_type(4)));
-constexpr int kThrU = 4;   // quads per lane per round (all loads first)
-
+//
+// The gradient and the dense result are float, or bfloat16 as 16-bit patterns (GT = uint16_t,
+// grace_threshold_step_w1_bf16): g is widened exactly, t, r, r', the partials and meta are f32 and bit
+// for bit the f32 instantiation's for the widened gradient, and out = bf16(0 + t | 0), rounded once.
+// A lane's unit is GradIo's: with memory the f32 kernel's four elements (8 B of g and of out beside the
+// quad of r), without memory eight (16 B of g, 16 B of out).  The vector path needs g, r and out
+// 16-byte aligned (a chunk starts a multiple of 16384 elements in, so every unit of it is aligned
+// then); any other alignment takes the scalar loop for the whole chunk.
 __device__ __forceinline__ void thr_sel(float t, float bound, float& o, float& rr) {
   const bool sel = fabsf(t) >= bound;
   o = sel ? 0.f + t : 0.f;
   rr = sel ? t - t : t;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(kSBlock) void thr_spec_kernel(const float* __restrict__ g, float* __restrict__ r,
+template <int MODE, typename GT>
+__global__ __launch_bounds__(kSBlock) void thr_spec_kernel(const GT* __restrict__ g, float* __restrict__ r,
                                                           float beta, float gamma, int64_t n, float thr,
-                                                          float* __restrict__ out, ThrPart* __restrict__ part,
+                                                          GT* __restrict__ out, ThrPart* __restrict__ part,
                                                           uint32_t* __restrict__ meta) {
+  typedef GradIo<GT, MODE == 0> Io;
+  typedef typename Io::vec gvec;
+  constexpr int EL = Io::EL, U = Io::U, RQ = EL / 4;
+  struct RUnit { f4s q[RQ]; };   // the f32 quads of r beside one unit of g
   __shared__ float sm[kSBlock / kWave];
   __shared__ uint32_t sn[kSBlock / kWave];
   __shared__ uint32_t s_last;
@@ -329,79 +506,92 @@ __global__ __launch_bounds__(kSBlock) void thr_spec_kernel(const float* __restri
   const int64_t end = min(base + (int64_t)kThrChunk, n);
   const bool vec = ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(r) |
                      reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
-  const int64_t qe = vec ? base + ((end - base) & ~(int64_t)3) : base;   // [base, qe) in quads
+  const int64_t qe = vec ? base + ((end - base) & ~(int64_t)(EL - 1)) : base;   // [base, qe) in units
   float mx = -INFINITY;
   uint32_t nan = 0;
   auto acc = [&](float v) { if (v != v) nan = 1; else mx = fmaxf(mx, v); };
-  auto process = [&](int64_t e, const f4s& gq, const f4s& rq) {
-    f4s t = gq;
-    if (MODE == 2) t = f4s{beta * rq.x + gamma * gq.x, beta * rq.y + gamma * gq.y, beta * rq.z + gamma * gq.z,
-                           beta * rq.w + gamma * gq.w};
-    f4s o, rr;
+  auto load_r = [&](int64_t e, RUnit& ru) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      acc(t[j]);
-      float oj, rj;
-      thr_sel(t[j], thr, oj, rj);
+    for (int h = 0; h < RQ; ++h) ru.q[h] = __builtin_nontemporal_load(reinterpret_cast<const f4s*>(r + e) + h);
+  };
+  auto process = [&](int64_t e, const gvec& gq, const RUnit& ru) {
+    float o[EL];
+    RUnit rr;
+#pragma unroll
+    for (int j = 0; j < EL; ++j) {
+      const float gj = Io::at(gq, j);
+      float t = gj;
+      if (MODE == 2) t = beta * ru.q[j >> 2][j & 3] + gamma * gj;
+      acc(t);
+      float oj, nj;
+      thr_sel(t, thr, oj, nj);
       o[j] = oj;
-      rr[j] = rj;
+      rr.q[j >> 2][j & 3] = nj;
     }
-    __builtin_nontemporal_store(o, reinterpret_cast<f4s*>(out + e));
-    if (MODE != 0) __builtin_nontemporal_store(rr, reinterpret_cast<f4s*>(r + e));
+    __builtin_nontemporal_store(Io::pack(o), reinterpret_cast<gvec*>(out + e));
+    if (MODE != 0) {
+#pragma unroll
+      for (int h = 0; h < RQ; ++h) __builtin_nontemporal_store(rr.q[h], reinterpret_cast<f4s*>(r + e) + h);
+    }
   };
   if (qe - base == kThrChunk) {
     // a whole chunk: a compile-time number of rounds, the next round's loads issued before the
-    // current round is processed (8 or 16 x 16 B in flight per lane, no guarded loads)
-    constexpr int NR = kThrChunk / (4 * kSBlock * kThrU);
-    const int64_t b0 = base + 4 * (int64_t)threadIdx.x;
-    f4s gv[kThrU], rv[kThrU];
+    // current round is processed (8 or 16 x 16 B in flight per lane in f32; no guarded
+    // loads)
+    constexpr int NR = kThrChunk / (EL * kSBlock * U);
+    const int64_t b0 = base + EL * (int64_t)threadIdx.x;
+    gvec gv[U];
+    RUnit rv[U];
 #pragma unroll
-    for (int u = 0; u < kThrU; ++u) {
-      gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f4s*>(g + b0 + 4 * (int64_t)u * kSBlock));
-      if (MODE == 2) rv[u] = __builtin_nontemporal_load(reinterpret_cast<const f4s*>(r + b0 + 4 * (int64_t)u * kSBlock));
+    for (int u = 0; u < U; ++u) {
+      gv[u] = __builtin_nontemporal_load(reinterpret_cast<const gvec*>(g + b0 + EL * (int64_t)u * kSBlock));
+      if (MODE == 2) load_r(b0 + EL * (int64_t)u * kSBlock, rv[u]);
     }
 #pragma unroll
     for (int q = 0; q < NR; ++q) {
-      const int64_t e0 = b0 + (int64_t)q * 4 * kSBlock * kThrU;
-      f4s gn[kThrU], rn[kThrU];
+      const int64_t e0 = b0 + (int64_t)q * EL * kSBlock * U;
+      gvec gn[U];
+      RUnit rn[U];
       if (q + 1 < NR) {
 #pragma unroll
-        for (int u = 0; u < kThrU; ++u) {
-          const int64_t e = e0 + 4 * (int64_t)kSBlock * kThrU + 4 * (int64_t)u * kSBlock;
-          gn[u] = __builtin_nontemporal_load(reinterpret_cast<const f4s*>(g + e));
-          if (MODE == 2) rn[u] = __builtin_nontemporal_load(reinterpret_cast<const f4s*>(r + e));
+        for (int u = 0; u < U; ++u) {
+          const int64_t e = e0 + EL * (int64_t)kSBlock * U + EL * (int64_t)u * kSBlock;
+          gn[u] = __builtin_nontemporal_load(reinterpret_cast<const gvec*>(g + e));
+          if (MODE == 2) load_r(e, rn[u]);
         }
       }
 #pragma unroll
-      for (int u = 0; u < kThrU; ++u) process(e0 + 4 * (int64_t)u * kSBlock, gv[u], rv[u]);
+      for (int u = 0; u < U; ++u) process(e0 + EL * (int64_t)u * kSBlock, gv[u], rv[u]);
       if (q + 1 < NR) {
 #pragma unroll
-        for (int u = 0; u < kThrU; ++u) { gv[u] = gn[u]; rv[u] = rn[u]; }
+        for (int u = 0; u < U; ++u) { gv[u] = gn[u]; rv[u] = rn[u]; }
       }
     }
   } else {
-    for (int64_t e0 = base + 4 * (int64_t)threadIdx.x; e0 < qe; e0 += 4 * (int64_t)kSBlock * kThrU) {
-      f4s gv[kThrU], rv[kThrU];
+    for (int64_t e0 = base + EL * (int64_t)threadIdx.x; e0 < qe; e0 += EL * (int64_t)kSBlock * U) {
+      gvec gv[U];
+      RUnit rv[U];
 #pragma unroll
-      for (int u = 0; u < kThrU; ++u) {
-        const int64_t e = e0 + 4 * (int64_t)u * kSBlock < qe ? e0 + 4 * (int64_t)u * kSBlock : e0;
-        gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f4s*>(g + e));
-        if (MODE == 2) rv[u] = __builtin_nontemporal_load(reinterpret_cast<const f4s*>(r + e));
+      for (int u = 0; u < U; ++u) {
+        const int64_t e = e0 + EL * (int64_t)u * kSBlock < qe ? e0 + EL * (int64_t)u * kSBlock : e0;
+        gv[u] = __builtin_nontemporal_load(reinterpret_cast<const gvec*>(g + e));
+        if (MODE == 2) load_r(e, rv[u]);
       }
 #pragma unroll
-      for (int u = 0; u < kThrU; ++u) {
-        const int64_t e = e0 + 4 * (int64_t)u * kSBlock;
+      for (int u = 0; u < U; ++u) {
+        const int64_t e = e0 + EL * (int64_t)u * kSBlock;
         if (e >= qe) break;
         process(e, gv[u], rv[u]);
       }
     }
   }
   for (int64_t i = qe + threadIdx.x; i < end; i += kSBlock) {
-    const float t = MODE == 2 ? beta * r[i] + gamma * g[i] : g[i];
+    const float gi = Io::widen(g[i]);
+    const float t = MODE == 2 ? beta * r[i] + gamma * gi : gi;
     acc(t);
     float o, rr;
     thr_sel(t, thr, o, rr);
-    out[i] = o;
+    out[i] = Io::narrow(o);
     if (MODE != 0) r[i] = rr;
   }
   // the chunk's (max, NaN) partial, write-through; the last workgroup to arrive decides the bound
@@ -452,24 +642,43 @@ __global__ __launch_bounds__(kSBlock) void thr_spec_kernel(const float* __restri
 }
 
 // fix-up pass: only when the speculative pass was wrong (max t < thr); returns at once otherwise
-template <int MODE>
-__global__ __launch_bounds__(kSBlock) void thr_fix_kernel(const float* __restrict__ g, float* __restrict__ r,
+//
+// A bfloat16 out has lost t's low bits where the speculative pass selected, so with memory the bf16
+// form never reads t back from it.  It does not need to: the fix-up runs only when bound = max t <
+// thr, so an element selected at thr (|t| >= thr) is selected at bound too, and its out = bf16(0 + t)
+// and r' = t - t (+0, or NaN for an infinite t) already stand.  Only the elements left alone are
+// decided again, and those have out = +0 and r' = t, exact in f32.  Which of the two an element is,
+// r' alone tells: a NaN r' was selected (a NaN t would have kept bound = thr: no fix-up), a non-zero
+// r' was left alone, and a zero r' is either a selected element, which stands, or t = +-0 left alone,
+// whose result if selected now is out = 0 + t = +0, as it is, and r' = t - t = +0 -- which is what the
+// selected element holds too.  So: r' == 0 -> r' = +0 if 0 >= bound; otherwise t = r' is decided at
+// bound, and only a newly selected element is written.
+template <int MODE, typename GT>
+__global__ __launch_bounds__(kSBlock) void thr_fix_kernel(const GT* __restrict__ g, float* __restrict__ r,
                                                          int64_t n, float thr, const uint32_t* __restrict__ meta,
-                                                         float* __restrict__ out) {
+                                                         GT* __restrict__ out) {
+  typedef GradIo<GT, false> Io;
   if (meta[2] == 0u) return;
   const float bound = __uint_as_float(meta[0]);
   for (int64_t i = (int64_t)blockIdx.x * kSBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kSBlock) {
-    float t;
-    if (MODE == 0) {
-      t = g[i];
-    } else {   // what the speculative pass wrote: out = 0 + t where it selected, r' = t elsewhere
-      const float o = out[i], rv = r[i];
-      t = fabsf(o) >= thr ? o : rv;
+    if constexpr (MODE != 0 && sizeof(GT) == 2) {
+      const float t = r[i];
+      if (t != t || !(fabsf(t) >= bound)) continue;
+      if (t != 0.f) out[i] = Io::narrow(0.f + t);
+      r[i] = t - t;
+    } else {
+      float t;
+      if (MODE == 0) {
+        t = Io::widen(g[i]);
+      } else {   // what the speculative pass wrote: out = 0 + t where it selected, r' = t elsewhere
+        const float o = out[i], rv = r[i];
+        t = fabsf(o) >= thr ? o : rv;
+      }
+      float o, rr;
+      thr_sel(t, bound, o, rr);
+      out[i] = Io::narrow(o);
+      if (MODE != 0) r[i] = rr;
     }
-    float o, rr;
-    thr_sel(t, bound, o, rr);
-    out[i] = o;
-    if (MODE != 0) r[i] = rr;
   }
 }
 
@@ -662,6 +871,32 @@ __global__ __launch_bounds__(kSBlock) void rec_sub_kernel(const uint32_t* __rest
     r[idx[j]] = r[idx[j]] - vals[j];
 }
 
+// grace_threshold_step_w1 and its bf16 twin: the speculative pass, then the gated fix-up
+template <typename GT>
+static grace_status_t threshold_step_w1(const char* name, const GT* g, float* residual, int32_t mode, float beta,
+                                        float gamma, int64_t n, float thr, void* ws, GT* out, hipStream_t s) {
+  const int64_t nch = (n + kThrChunk - 1) / kThrChunk;
+  char* p = reinterpret_cast<char*>(ws);
+  uint32_t* meta = reinterpret_cast<uint32_t*>(p);
+  ThrPart* part = reinterpret_cast<ThrPart*>(p + 64);
+  const unsigned fgrid = stream_grid(n, kSBlock, 1024);
+  if (mode == 0) {
+    thr_spec_kernel<0, GT><<<(unsigned)nch, kSBlock, 0, s>>>(g, nullptr, beta, gamma, n, thr, out, part, meta);
+    GRACE_CHECK_LAUNCH(name);
+    thr_fix_kernel<0, GT><<<fgrid, kSBlock, 0, s>>>(g, nullptr, n, thr, meta, out);
+  } else if (mode == 1) {
+    thr_spec_kernel<1, GT><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, thr, out, part, meta);
+    GRACE_CHECK_LAUNCH(name);
+    thr_fix_kernel<1, GT><<<fgrid, kSBlock, 0, s>>>(g, residual, n, thr, meta, out);
+  } else {
+    thr_spec_kernel<2, GT><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, thr, out, part, meta);
+    GRACE_CHECK_LAUNCH(name);
+    thr_fix_kernel<2, GT><<<fgrid, kSBlock, 0, s>>>(g, residual, n, thr, meta, out);
+  }
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
+
 }  // namespace grace
 
 using namespace grace;
@@ -774,6 +1009,71 @@ grace_status_t grace_randomk_step_w1_dense(const float* g, float* residual, int3
   return GRACE_OK;
 }
 
+grace_status_t grace_randomk_step_w1_dense_bf16(const uint16_t* g, float* residual, int32_t has_residual, float beta,
+                                                float gamma, int64_t n, const int64_t* idx, int64_t k, uint16_t* out,
+                                                void* ws, size_t ws_bytes, void* stream) {
+  GRACE_REQUIRE(g && residual && out && ws && n >= 1 && n <= ((int64_t)1 << 28) && k >= 0 && (k == 0 || idx) &&
+                    ws_bytes >= grace_randomk_step_w1_dense_workspace_bytes(n, k),
+                "grace_randomk_step_w1_dense_bf16: bad arguments (1 <= n <= 2^28, workspace)");
+  const int64_t nch = (n + kRkChunk - 1) / kRkChunk;
+  hipStream_t s = as_stream(stream);
+  char* p = reinterpret_cast<char*>(ws);   // the f32 entry's workspace layout: scratch, then the grouping
+  uint32_t* scratch = reinterpret_cast<uint32_t*>(p);
+  char* q = p + group_scratch_bytes(nch);
+  uint32_t* ends = reinterpret_cast<uint32_t*>(q);
+  uint16_t* offs = reinterpret_cast<uint16_t*>(q + ((sizeof(uint32_t) * (size_t)nch + 255) & ~(size_t)255));
+  const hipError_t e = group_by_chunk<int64_t>(nullptr, idx, k, nch, nullptr, offs, ends, scratch, s);
+  if (e != hipSuccess) { set_error("grace_randomk_step_w1_dense_bf16", e); return GRACE_ERR_HIP; }
+  if (has_residual)
+    randomk_dense_pass_bf16_kernel<true><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, offs, ends, out);
+  else
+    randomk_dense_pass_bf16_kernel<false><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, offs, ends, out);
+  GRACE_CHECK_LAUNCH("grace_randomk_step_w1_dense_bf16");
+  return GRACE_OK;
+}
+
+// r'[idx[j]] = vals[j] - vals[j] where vals = t[idx] was gathered before (ResidualMemory.update after a
+// random-k compress, residual.py:16-20: +0, or NaN where t is infinite or NaN).  Duplicates of an index
+// carry the same value, so their writes agree; an index outside [0, n) is skipped.
+grace_status_t grace_randomk_clear(const int64_t* idx, const float* vals, int64_t k, float* r, int64_t n, void* stream) {
+  GRACE_REQUIRE(k >= 0 && n >= 1 && r && (k == 0 || (idx && vals)), "grace_randomk_clear: bad arguments");
+  if (k == 0) return GRACE_OK;
+  randomk_shard_scatter_kernel<<<stream_grid(k, kSBlock, 2048), kSBlock, 0, as_stream(stream)>>>(idx, vals, k, 0, n, r,
+                                                                                                  nullptr);
+  GRACE_CHECK_LAUNCH("grace_randomk_clear");
+  return GRACE_OK;
+}
+
+// World > 1 Allgather(RandomK).send_receive on a bfloat16 gradient: every rank drew the same idx[k], and
+// vals[w][j] is rank w's t[idx[j]].  out[idx[j]] = bf16((((0 + v0[j]) + v1[j]) + ...) / divisor), +0
+// elsewhere: a fill, then one scatter.  Duplicates of an index carry equal values on every rank (each
+// rank gathered them from its own t before anything was cleared), so they compute the same 16 bits and
+// the order of their writes cannot matter.  An index outside [0, n) is skipped.
+grace_status_t grace_randomk_aggregate_bf16(const float* vals, const int64_t* idx, int64_t k, int32_t world,
+                                            float divisor, uint16_t* out, int64_t n, void* stream) {
+  GRACE_REQUIRE(out && n >= 1 && k >= 0 && world >= 1 && (k == 0 || (vals && idx)),
+                "grace_randomk_aggregate_bf16: bad arguments");
+  grace_status_t st = grace_fill_bf16(out, 0, n, stream);
+  if (st != GRACE_OK || k == 0) return st;
+  randomk_aggregate_bf16_kernel<<<stream_grid(k, kSBlock, 2048), kSBlock, 0, as_stream(stream)>>>(vals, idx, k, world,
+                                                                                                   divisor, out, n);
+  GRACE_CHECK_LAUNCH("grace_randomk_aggregate_bf16");
+  return GRACE_OK;
+}
+
+// t = beta r + gamma widen(g) into an f32 buffer (ResidualMemory.compensate on a bfloat16 gradient, the
+// world > 1 steps); has_residual = 0: the widening copy of a name's first step (r unused).  t may be r.
+grace_status_t grace_axpby_bf16(const float* r, const uint16_t* g, int32_t has_residual, float beta, float gamma,
+                                float* t, int64_t n, void* stream) {
+  GRACE_REQUIRE(n >= 0 && g && t && (!has_residual || r), "grace_axpby_bf16: bad arguments");
+  if (n == 0) return GRACE_OK;
+  const unsigned grid = stream_grid((n + 3) / 4, kSBlock);
+  if (has_residual) axpby_bf16_kernel<true><<<grid, kSBlock, 0, as_stream(stream)>>>(r, g, beta, gamma, t, n);
+  else axpby_bf16_kernel<false><<<grid, kSBlock, 0, as_stream(stream)>>>(r, g, beta, gamma, t, n);
+  GRACE_CHECK_LAUNCH("grace_axpby_bf16");
+  return GRACE_OK;
+}
+
 grace_status_t grace_gather(const float* x, const int64_t* idx, int64_t k, float* vals, void* stream) {
   GRACE_REQUIRE(x && idx && vals && k >= 0, "grace_gather: bad arguments");
   if (k == 0) return GRACE_OK;
@@ -808,30 +1108,18 @@ grace_status_t grace_threshold_step_w1(const float* g, float* residual, int32_t 
                                        int64_t n, float thr, void* ws, float* out, void* stream) {
   GRACE_REQUIRE(g && out && ws && n >= 1 && mode >= 0 && mode <= 2 && (mode == 0 || residual),
                 "grace_threshold_step_w1: bad arguments");
-  const int64_t nch = (n + kThrChunk - 1) / kThrChunk;
-  char* p = reinterpret_cast<char*>(ws);
-  uint32_t* meta = reinterpret_cast<uint32_t*>(p);
-  ThrPart* part = reinterpret_cast<ThrPart*>(p + 64);
-  uint32_t* offs = reinterpret_cast<uint32_t*>(p + 64 + sizeof(ThrPart) * nch);
-  (void)offs;
-  hipStream_t s = as_stream(stream);
-  GRACE_REQUIRE(nch < (int64_t)1 << 31, "grace_threshold_step_w1: too many chunks");
-  const unsigned fgrid = stream_grid(n, kSBlock, 1024);
-  if (mode == 0) {
-    thr_spec_kernel<0><<<(unsigned)nch, kSBlock, 0, s>>>(g, nullptr, beta, gamma, n, thr, out, part, meta);
-    GRACE_CHECK_LAUNCH("grace_threshold_step_w1");
-    thr_fix_kernel<0><<<fgrid, kSBlock, 0, s>>>(g, nullptr, n, thr, meta, out);
-  } else if (mode == 1) {
-    thr_spec_kernel<1><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, thr, out, part, meta);
-    GRACE_CHECK_LAUNCH("grace_threshold_step_w1");
-    thr_fix_kernel<1><<<fgrid, kSBlock, 0, s>>>(g, residual, n, thr, meta, out);
-  } else {
-    thr_spec_kernel<2><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, thr, out, part, meta);
-    GRACE_CHECK_LAUNCH("grace_threshold_step_w1");
-    thr_fix_kernel<2><<<fgrid, kSBlock, 0, s>>>(g, residual, n, thr, meta, out);
-  }
-  GRACE_CHECK_LAUNCH("grace_threshold_step_w1");
-  return GRACE_OK;
+  GRACE_REQUIRE((n + kThrChunk - 1) / kThrChunk < (int64_t)1 << 31, "grace_threshold_step_w1: too many chunks");
+  return threshold_step_w1<float>("grace_threshold_step_w1", g, residual, mode, beta, gamma, n, thr, ws, out,
+                                  as_stream(stream));
+}
+
+grace_status_t grace_threshold_step_w1_bf16(const uint16_t* g, float* residual, int32_t mode, float beta, float gamma,
+                                            int64_t n, float thr, void* ws, uint16_t* out, void* stream) {
+  GRACE_REQUIRE(g && out && ws && n >= 1 && mode >= 0 && mode <= 2 && (mode == 0 || residual),
+                "grace_threshold_step_w1_bf16: bad arguments");
+  GRACE_REQUIRE((n + kThrChunk - 1) / kThrChunk < (int64_t)1 << 31, "grace_threshold_step_w1_bf16: too many chunks");
+  return threshold_step_w1<uint16_t>("grace_threshold_step_w1_bf16", g, residual, mode, beta, gamma, n, thr, ws, out,
+                                     as_stream(stream));
 }
 
 // Recount at max(x) (only when max(x) < thr, flagged by stage 1).

@@ -1356,6 +1356,129 @@ def threshold_compress_strict(x, thr):
     return vals, idx
 
 
+# ------------------------------------------- threshold / random-k on bfloat16 (include/grace_hip_sparse.h)
+def _bf16_step_residual(residual, n, device, what):
+    if not _f32_residual(residual, n, device):
+        raise TypeError(f"grace_amd: {what}: the residual must be a contiguous float32 tensor of {n} elements on "
+                        f"{device}")
+    return residual
+
+
+def threshold_step_w1(g, residual, mode, beta, gamma, thr, out=None):
+    """World-1 Allgather(Threshold, NoneMemory | ResidualMemory).step without a payload
+    (grace_threshold_step_w1, grace_threshold_step_w1_bf16): g float32 or bfloat16, the dense result
+    in g's dtype (a new tensor unless `out` is given).  mode 0: no memory; 1: a name's first step
+    (r' written to `residual`); 2: t = beta r + gamma g with r read from `residual` and r' written
+    back.  `residual` is f32 whatever g is; the bound and the fix-up flag stay in
+    workspace("threshold")."""
+    import numpy as np
+    g = dev_grad(g)
+    n, mode = g.numel(), int(mode)
+    if mode not in (0, 1, 2) or n < 1:
+        raise ValueError(f"grace_amd: threshold_step_w1: mode must be 0, 1 or 2 and the gradient non-empty, got mode="
+                         f"{mode}, n={n}")
+    if mode != 0:
+        _bf16_step_residual(residual, n, g.device, "threshold_step_w1")
+    out = _out_buf(out, n, g.dtype, g.device, "grace_amd: threshold_step_w1")
+    ws = workspace("threshold", _lib.query("grace_threshold_workspace_bytes", n), g.device)
+    _lib.call(_entry("grace_threshold_step_w1", g.dtype), _p(g), _p(residual) if mode != 0 else None, mode, float(beta),
+              float(gamma), n, float(np.float32(thr)), _p(ws), _p(out), _stream())
+    return out
+
+
+def axpby_grad(r, g, beta, gamma, out=None):
+    """t = beta r + gamma g as a flat float32 tensor, g float32 or bfloat16 (widened exactly;
+    grace_axpby_bf16).  r None: a name's first step, t = g in f32 (a copy)."""
+    g = dev_grad(g)
+    n = g.numel()
+    if r is not None:
+        _bf16_step_residual(r, n, g.device, "axpby_grad")
+    out = _out_buf(out, n, F32, g.device, "grace_amd: axpby_grad")
+    if g.dtype == F32:
+        if r is None:
+            return out.copy_(g)
+        _lib.call("grace_axpby", _p(r), _p(g), float(beta), float(gamma), _p(out), n, _stream())
+    elif n:
+        _lib.call("grace_axpby_bf16", _p(r), _p(g), 1 if r is not None else 0, float(beta), float(gamma), _p(out), n,
+                  _stream())
+    return out
+
+
+def randomk_step_w1_dense_bf16(g, residual, has_residual, beta, gamma, idx, out=None):
+    """randomk_step_w1_dense on a bfloat16 gradient: the bf16 dense result (a new tensor unless `out` is
+    given, written in full: no recycled output) and r' in the f32 `residual`
+    (grace_randomk_step_w1_dense_bf16).  At most 2^28 elements."""
+    g = dev_grad(g)
+    if g.dtype != BF16:
+        raise TypeError(f"grace_amd: randomk_step_w1_dense_bf16 takes a bfloat16 gradient, got {g.dtype}")
+    n = g.numel()
+    _bf16_step_residual(residual, n, g.device, "randomk_step_w1_dense_bf16")
+    idx = require_dev(idx, "indices")
+    if idx.dtype != torch.int64:
+        raise ValueError("grace_amd: random-k indices are int64")
+    if not 1 <= n <= SORT_PAYLOAD_MAX_N:
+        raise ValueError(f"grace_amd: randomk_step_w1_dense_bf16 takes 1 to 2^28 elements, got {n}")
+    out = _bf16_out(out, n, g.device, "randomk_step_w1_dense_bf16")
+    k = idx.numel()
+    ws = workspace("randomk_w1", _lib.query("grace_randomk_step_w1_dense_workspace_bytes", n, k), g.device)
+    _lib.call("grace_randomk_step_w1_dense_bf16", _p(g), _p(residual), 1 if has_residual else 0, float(beta),
+              float(gamma), n, _p(idx), k, _p(out), _p(ws), ws.numel(), _stream())
+    return out
+
+
+def randomk_clear(r, idx, vals):
+    """r[idx] = vals - vals in place, vals = gather(r, idx) taken before (grace_randomk_clear): the
+    residual of a random-k step once its payload is taken."""
+    r, vals = dev_f32(r, "residual"), dev_f32(vals, "values")
+    idx = require_dev(idx, "indices")
+    if idx.dtype != torch.int64 or idx.numel() != vals.numel():
+        raise ValueError("grace_amd: randomk_clear: one int64 index per value")
+    _lib.call("grace_randomk_clear", _p(idx), _p(vals), idx.numel(), _p(r), r.numel(), _stream())
+    return r
+
+
+def randomk_aggregate(vals, idx, world, n, divisor, out_dtype=BF16):
+    """The world > 1 decode of random-k as a bfloat16 dense result (grace_randomk_aggregate_bf16):
+    vals = the `world` gathered payloads (rank-major, idx.numel() values each), idx the indices every
+    rank drew; out[idx] = bf16((((0 + v0) + v1) + ...) / divisor), +0 elsewhere."""
+    if out_dtype != BF16:
+        raise TypeError(f"grace_amd: randomk_aggregate writes bfloat16, got {out_dtype}")
+    vals = dev_f32(vals, "values")
+    idx = require_dev(idx, "indices")
+    world, n, k = int(world), int(n), idx.numel()
+    if idx.dtype != torch.int64 or world < 1 or n < 1 or vals.numel() != world * k:
+        raise ValueError("grace_amd: randomk_aggregate: int64 indices and world x k values over n >= 1 elements")
+    out = torch.empty(n, dtype=BF16, device=vals.device)
+    _lib.call("grace_randomk_aggregate_bf16", _p(vals), _p(idx), k, world, float(divisor), _p(out), n, _stream())
+    return out
+
+
+def sparse_aggregate_padded(buf, cap, counts_dev, world, n, divisor, out_dtype=BF16):
+    """Rank-ordered decode+aggregate of the padded buffers of the threshold counts exchange as a
+    bfloat16 dense result (grace_sparse_aggregate_padded_bf16): rank w's block of 2 cap words of `buf`
+    is [vals f32[cap] | idx i32[cap]], its count counts_dev[w] (int32 on the device: nothing is read
+    on the host); indices ascend within a rank.  1 <= cap <= n < 2^31, world <= 1024."""
+    if out_dtype != BF16:
+        raise TypeError(f"grace_amd: sparse_aggregate_padded writes bfloat16, got {out_dtype}")
+    require_dev(buf, "payloads")
+    require_dev(counts_dev, "counts")
+    world, cap, n = int(world), int(cap), int(n)
+    if buf.dtype not in (F32, torch.int32) or counts_dev.dtype != torch.int32:
+        raise TypeError("grace_amd: sparse_aggregate_padded: payloads are 4-byte words (float32 / int32), counts int32")
+    if not (1 <= cap <= n < 2 ** 31 and 1 <= world <= RECORDS_BF16_MAX_WORLD):
+        raise ValueError("grace_amd: sparse_aggregate_padded needs 1 <= cap <= n < 2^31 and "
+                         f"1 <= world <= {RECORDS_BF16_MAX_WORLD}, got cap={cap}, n={n}, world={world}")
+    if buf.numel() < world * 2 * cap or counts_dev.numel() < world or not buf.is_contiguous() \
+            or not counts_dev.is_contiguous():
+        raise ValueError("grace_amd: sparse_aggregate_padded: payloads / counts do not match (world, cap)")
+    out = torch.empty(n, dtype=BF16, device=buf.device)
+    nbytes = _lib.query("grace_sparse_aggregate_padded_bf16_workspace_bytes", world, n)
+    ws = workspace("records_bf16", nbytes, buf.device)
+    _lib.call("grace_sparse_aggregate_padded_bf16", _p(buf), cap, _p(counts_dev), world, float(divisor), _p(out), n,
+              _p(ws), nbytes, _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- PowerSGD
 def _dev_mat(t, what):
     """A PowerSGD operand the kernels read through its data pointer: on the GPU, float32 and made

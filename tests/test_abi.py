@@ -2,17 +2,14 @@
 (no compute calls here)."""
 import ctypes
 import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_util import HEADERS, check_types, declared, header
 
 
 def declared_functions():
-    hdr = open(os.path.join(ROOT, "include", "grace_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(grace_[a-z0-9_]+)\s*\(", hdr)))
+    return declared(header("grace_hip.h"))
 
 
 def test_header_declares_functions():
@@ -32,6 +29,16 @@ def test_library_exports_every_declared_symbol():
 def test_binding_table_matches_header():
     from grace_amd import _lib
     assert sorted(_lib.SIGNATURES) == declared_functions()
+
+
+@pytest.mark.parametrize("name,table", zip(HEADERS, ("SIGNATURES", "SIGNATURES_SIGN", "SIGNATURES_QUANT",
+                                                     "SIGNATURES_DGC", "SIGNATURES_SPARSE")))
+def test_binding_table_types_match_prototypes(name, table):
+    """All 191 entries, by a reading of the prototypes that is not the binding's own parser."""
+    from grace_amd import _lib
+    hdr = header(name)
+    assert sorted(getattr(_lib, table)) == declared(hdr)
+    check_types(hdr, getattr(_lib, table))
 
 
 def test_version_and_error_channel():

@@ -1,12 +1,12 @@
 """The bfloat16 top-k entry points are declared in include/grace_hip.h, exported by the library
 and bound in grace_amd/_lib.py, and refuse bad arguments without touching the device (no GPU)."""
 import ctypes
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_util import header
+
 NAMES = ["grace_topk_compress_bf16", "grace_topk_step_dense_bf16", "grace_topk_residual_step_bf16",
          "grace_topk_residual_step_swap_bf16", "grace_f32_to_bf16"]
 
@@ -14,8 +14,7 @@ NAMES = ["grace_topk_compress_bf16", "grace_topk_step_dense_bf16", "grace_topk_r
 @pytest.mark.parametrize("name", NAMES)
 def test_bf16_entry_point_declared_exported_bound(name):
     from grace_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "grace_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = header("grace_hip.h")
     assert re.search(r"\b%s\s*\(" % name, hdr), "not declared in include/grace_hip.h"
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), name), "not exported by the library"
     assert name in _lib.SIGNATURES, "not bound in grace_amd/_lib.py"

@@ -2,20 +2,19 @@
 refuses bad arguments without touching the device; the Python pieces of the bf16 Allgather step that
 need no GPU (ops.sparse_aggregate_sorted's out_dtype check, grace_amd.topk_bf16's class)."""
 import ctypes
-import os
 import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_util import header
+
 NAME = "grace_sparse_aggregate_sorted_bf16"
 
 
 def test_entry_point_declared_exported_bound():
     from grace_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "grace_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = header("grace_hip.h")
     m = re.search(r"\b%s\s*\(([^)]*)\)" % NAME, hdr)
     assert m, "not declared in include/grace_hip.h"
     f32 = re.search(r"\bgrace_sparse_aggregate_sorted\s*\(([^)]*)\)", hdr).group(1)

@@ -8,16 +8,15 @@ import ctypes
 import inspect
 import os
 import re
-import textwrap
 
 import numpy as np
 import pytest
 import torch
 
+from tests.abi_util import ROOT, OnGpu, body, check_bad, declared, header, no_native, params
 from tests.dgc_bf16_util import LOOP_PATH_HOLDS, LOOP_PATH_LOST, rounded_case, world2_grad
 from tests.dgc_edge_util import LOOP_CASES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # f32 form -> its parameters that become uint16_t* in the twin
 TWINS = {
     "grace_dgc_step_w1_fused": ("const float* g", "float* out"),
@@ -31,26 +30,11 @@ DECODE = ("grace_sparse_aggregate_records_bf16", "grace_sparse_aggregate_records
 NEW = tuple(sorted([f + "_bf16" for f in TWINS] + list(DECODE)))
 
 
-def _header(name):
-    hdr = open(os.path.join(ROOT, "include", name)).read()
-    return re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-
-def _declared(hdr):
-    return sorted(set(re.findall(r"\b(grace_[a-z0-9_]+)\s*\(", hdr)))
-
-
-def _params(hdr, name):
-    m = re.search(r"\b%s\s*\(([^)]*)\)" % name, hdr)
-    assert m, f"{name} is not declared"
-    return re.sub(r"\s+", " ", m.group(1)).strip()
-
-
 def test_entry_points_declared_exported_bound():
     from grace_amd import _lib
-    dgc = _header("grace_hip_dgc.h")
+    dgc = header("grace_hip_dgc.h")
     assert '#include "grace_hip.h"' in dgc and 'extern "C"' in dgc
-    assert _declared(dgc) == sorted(NEW) == sorted(_lib.SIGNATURES_DGC)
+    assert declared(dgc) == sorted(NEW) == sorted(_lib.SIGNATURES_DGC)
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in NEW:
         assert hasattr(lib, name), f"{name} is not exported by the library"
@@ -58,7 +42,7 @@ def test_entry_points_declared_exported_bound():
     for name, (res, args) in _lib.SIGNATURES_DGC.items():
         f = getattr(bound, name)
         assert f.restype == res and list(f.argtypes) == args, name
-        assert len(args) == _params(dgc, name).count(",") + 1, name
+        assert len(args) == params(dgc, name).count(",") + 1, name
     raw = open(os.path.join(ROOT, "include", "grace_hip_dgc.h")).read()
     for name in NEW:   # a doc comment right above every entry point
         assert re.search(r"\*/\s*\n[a-z_ ]+\b%s\(" % name, raw), f"{name} has no doc comment"
@@ -66,31 +50,22 @@ def test_entry_points_declared_exported_bound():
 
 def test_first_three_headers_and_tables_are_unchanged():
     from grace_amd import _lib
-    for header, table, count in (("grace_hip.h", _lib.SIGNATURES, 159), ("grace_hip_sign.h", _lib.SIGNATURES_SIGN, 11),
-                                 ("grace_hip_quant.h", _lib.SIGNATURES_QUANT, 6)):
-        names = _declared(_header(header))
-        assert len(names) == count and len(table) == count and sorted(table) == names, header
+    for h, table, count in (("grace_hip.h", _lib.SIGNATURES, 159), ("grace_hip_sign.h", _lib.SIGNATURES_SIGN, 11),
+                            ("grace_hip_quant.h", _lib.SIGNATURES_QUANT, 6)):
+        names = declared(header(h))
+        assert len(names) == count and len(table) == count and sorted(table) == names, h
         assert not set(NEW) & set(names)
 
 
 @pytest.mark.parametrize("f32", sorted(TWINS))
 def test_bf16_twin_mirrors_the_f32_entry_point(f32):
     from grace_amd import _lib
-    want = _params(_header("grace_hip.h"), f32)
+    want = params(header("grace_hip.h"), f32)
     for s in TWINS[f32]:
         assert want.count(s) == 1, (f32, s)
         want = want.replace(s, s.replace("float*", "uint16_t*"))
-    assert _params(_header("grace_hip_dgc.h"), f32 + "_bf16") == want
+    assert params(header("grace_hip_dgc.h"), f32 + "_bf16") == want
     assert _lib.SIGNATURES_DGC[f32 + "_bf16"] == _lib.SIGNATURES[f32]
-
-
-def _check_bad(lib, name, good, bad):
-    f = getattr(lib, name)
-    for i, v in bad:
-        args = list(good)
-        args[i] = v
-        assert f(*args) == -1, (name, i, v)
-        assert lib.grace_last_error().startswith(name.encode() + b":"), lib.grace_last_error()
 
 
 def test_argument_errors_do_not_touch_the_device():
@@ -108,33 +83,33 @@ def test_argument_errors_do_not_touch_the_device():
     good = [p, q, r, 1, 0.9, 16, p, 1, 0.01, p, s, s + 64, p, None]
     bad = [(0, None), (1, None), (2, None), (6, None), (9, None), (10, None), (11, None), (12, None), (5, 0), (5, -1),
            (5, 1 << 40), (7, 0), (10, q), (11, r), (11, s)]
-    _check_bad(lib, name, good, bad)
+    check_bad(lib, name, good, bad)
 
     # g, residual, accum, has_state, momentum, n, sample_idx, seed, ns, sample_abs, stream
     name = "grace_dgc_sample_comp_bf16"
     good = [p, q, r, 1, 0.9, 16, None, 1, 4, s, None]
-    _check_bad(lib, name, good, [(0, None), (1, None), (2, None), (9, None), (5, 0), (5, -1), (8, 0), (8, -1)])
+    check_bad(lib, name, good, [(0, None), (1, None), (2, None), (9, None), (5, 0), (5, -1), (8, 0), (8, -1)])
 
     # g, residual, accum, has_state, momentum, n, stream
     name = "grace_dgc_compensate_bf16"
     good = [p, q, r, 1, 0.9, 16, None]
-    _check_bad(lib, name, good, [(0, None), (1, None), (2, None), (5, -1), (2, q)])
+    check_bad(lib, name, good, [(0, None), (1, None), (2, None), (5, -1), (2, q)])
     good[5] = 0
     assert getattr(lib, name)(*good) == 0
 
     # t, residual, accum, n, ws, out, stream
     name = "grace_dgc_step_w1_bf16"
     good = [p, q, r, 16, p, s, None]
-    _check_bad(lib, name, good, [(0, None), (1, None), (2, None), (4, None), (5, None), (3, -1), (2, q)])
+    check_bad(lib, name, good, [(0, None), (1, None), (2, None), (4, None), (5, None), (3, -1), (2, q)])
     good[3] = 0
     assert getattr(lib, name)(*good) == 0
 
     # x, n, ws, out, stream
-    _check_bad(lib, "grace_sumsq_bf16", [p, 16, q, r, None], [(0, None), (2, None), (3, None), (1, -1)])
+    check_bad(lib, "grace_sumsq_bf16", [p, 16, q, r, None], [(0, None), (2, None), (3, None), (1, -1)])
     # x, sumsq_dev, world, out, n, stream
     name = "grace_clip_by_sumsq_bf16"
     good = [p, q, 2.0, r, 16, None]
-    _check_bad(lib, name, good, [(0, None), (1, None), (3, None), (4, -1), (2, 0.0), (2, -1.0)])
+    check_bad(lib, name, good, [(0, None), (1, None), (3, None), (4, -1), (2, 0.0), (2, -1.0)])
     good[4] = 0
     assert getattr(lib, name)(*good) == 0
 
@@ -146,27 +121,12 @@ def test_argument_errors_do_not_touch_the_device():
     good = [p, 4 + 2 * 8, 8, 2, 2.0, q, 100, r, s, wsb(2, 100), None]
     bad = [(0, None), (5, None), (7, None), (8, None), (1, 4 + 2 * 8 + 1), (2, 0), (2, -1), (2, 101), (3, 0), (3, -1),
            (3, 1025), (6, 0), (6, 7), (6, 1 << 31), (9, 0), (9, wsb(2, 100) - 1)]
-    _check_bad(lib, name, good, bad)
-
-
-class OnGpu(torch.Tensor):
-    """A CPU tensor that says it is on the GPU, so that the wrappers get as far as their own checks."""
-    device = property(lambda self: torch.device("cuda", 0))
-    is_cuda = property(lambda self: True)
-
-
-def _no_native(monkeypatch):
-    from grace_amd import _lib
-
-    def no_native(*a, **kw):
-        raise AssertionError("a native call was made")
-    for attr in ("call", "query", "fn", "load"):
-        monkeypatch.setattr(_lib, attr, no_native)
+    check_bad(lib, name, good, bad)
 
 
 def test_ops_check_dtypes_before_any_native_call(monkeypatch):
     from grace_amd import ops
-    _no_native(monkeypatch)
+    no_native(monkeypatch)
     f32 = torch.zeros(256)
     for dtype in (torch.float16, torch.float64, torch.int16):
         for x in (torch.zeros(256, dtype=dtype), torch.zeros(256, dtype=dtype).as_subclass(OnGpu)):
@@ -196,7 +156,7 @@ def test_ops_bf16_state_must_be_f32(monkeypatch):
     """The memory of a bf16 step is the f32 class's: a bf16, short or strided residual is a TypeError
     before any native call; the bf16 decode's limits are a ValueError."""
     from grace_amd import ops
-    _no_native(monkeypatch)
+    no_native(monkeypatch)
     g = torch.zeros(256, dtype=torch.bfloat16).as_subclass(OnGpu)
     ok = torch.zeros(256).as_subclass(OnGpu)
     for bad in (torch.zeros(256, dtype=torch.bfloat16).as_subclass(OnGpu), torch.zeros(255).as_subclass(OnGpu),
@@ -234,18 +194,12 @@ def test_class_is_the_dist_class():
         D.DgcCompressor(0.01, exchange="sizes")
 
 
-def _body(fn):
-    src = textwrap.dedent(inspect.getsource(fn))
-    src = re.sub(r'""".*?"""', "", src, count=1, flags=re.S)     # the docstring
-    return [ln.rstrip() for ln in src.split("\n")[1:] if ln.strip()]  # without the def line
-
-
 def test_exchange_step_is_the_parents_but_for_the_decode_dtype():
     """grace_amd/dist/ has no hook at the decode, so the stand-in repeats _exchange_step: its body is
     the parent's text with `out_dtype=out_dtype` added to the two decode calls, and nothing else."""
     from grace_amd import dgc_bf16 as D
     from grace_amd.dist.compressor.dgc import DgcCompressor
-    parent, ours = _body(DgcCompressor._exchange_step), _body(D.DgcCompressor._exchange_step)
+    parent, ours = body(DgcCompressor._exchange_step), body(D.DgcCompressor._exchange_step)
     assert sum("ops.sparse_aggregate_capped(" in ln for ln in parent) == 2
     want = [ln.replace(", stat)", ", stat, out_dtype=out_dtype)") if "ops.sparse_aggregate_capped(" in ln else ln
             for ln in parent]

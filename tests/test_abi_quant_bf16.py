@@ -9,7 +9,8 @@ import re
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_util import ROOT, OnGpu, check_bad, declared, header, no_native, params
+
 # f32 form -> its parameters that become uint16_t* in the twin
 TWINS = {
     "grace_qsgd_compress_at": ("const float* x",),
@@ -22,26 +23,11 @@ TWINS = {
 NEW = tuple(sorted(f + "_bf16" for f in TWINS))
 
 
-def _header(name):
-    hdr = open(os.path.join(ROOT, "include", name)).read()
-    return re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-
-def _declared(hdr):
-    return sorted(set(re.findall(r"\b(grace_[a-z0-9_]+)\s*\(", hdr)))
-
-
-def _params(hdr, name):
-    m = re.search(r"\b%s\s*\(([^)]*)\)" % name, hdr)
-    assert m, f"{name} is not declared"
-    return re.sub(r"\s+", " ", m.group(1)).strip()
-
-
 def test_entry_points_declared_exported_bound():
     from grace_amd import _lib
-    quant = _header("grace_hip_quant.h")
+    quant = header("grace_hip_quant.h")
     assert '#include "grace_hip.h"' in quant and 'extern "C"' in quant
-    assert _declared(quant) == sorted(NEW) == sorted(_lib.SIGNATURES_QUANT)
+    assert declared(quant) == sorted(NEW) == sorted(_lib.SIGNATURES_QUANT)
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in NEW:
         assert hasattr(lib, name), f"{name} is not exported by the library"
@@ -49,7 +35,7 @@ def test_entry_points_declared_exported_bound():
     for name, (res, args) in _lib.SIGNATURES_QUANT.items():
         f = getattr(bound, name)
         assert f.restype == res and list(f.argtypes) == args, name
-        assert len(args) == _params(quant, name).count(",") + 1, name
+        assert len(args) == params(quant, name).count(",") + 1, name
     raw = open(os.path.join(ROOT, "include", "grace_hip_quant.h")).read()
     for name in NEW:   # a doc comment right above every entry point
         assert re.search(r"\*/\s*\n[a-z_ ]+\b%s\(" % name, raw), f"{name} has no doc comment"
@@ -57,9 +43,9 @@ def test_entry_points_declared_exported_bound():
 
 def test_first_two_headers_and_tables_are_unchanged():
     from grace_amd import _lib
-    names = _declared(_header("grace_hip.h"))
+    names = declared(header("grace_hip.h"))
     assert len(names) == 159 and len(_lib.SIGNATURES) == 159 and sorted(_lib.SIGNATURES) == names
-    sign = _declared(_header("grace_hip_sign.h"))
+    sign = declared(header("grace_hip_sign.h"))
     assert len(sign) == 11 and len(_lib.SIGNATURES_SIGN) == 11 and sorted(_lib.SIGNATURES_SIGN) == sign
     for table in (names, sign, _lib.SIGNATURES, _lib.SIGNATURES_SIGN):
         assert not set(NEW) & set(table)
@@ -68,21 +54,12 @@ def test_first_two_headers_and_tables_are_unchanged():
 @pytest.mark.parametrize("f32", sorted(TWINS))
 def test_bf16_twin_mirrors_the_f32_entry_point(f32):
     from grace_amd import _lib
-    want = _params(_header("grace_hip.h"), f32)
+    want = params(header("grace_hip.h"), f32)
     for s in TWINS[f32]:
         assert want.count(s) == 1, (f32, s)
         want = want.replace(s, s.replace("float*", "uint16_t*"))
-    assert _params(_header("grace_hip_quant.h"), f32 + "_bf16") == want
+    assert params(header("grace_hip_quant.h"), f32 + "_bf16") == want
     assert _lib.SIGNATURES_QUANT[f32 + "_bf16"] == _lib.SIGNATURES[f32]
-
-
-def _check_bad(lib, name, good, bad):
-    f = getattr(lib, name)
-    for i, v in bad:
-        args = list(good)
-        args[i] = v
-        assert f(*args) == -1, (name, i, v)
-        assert lib.grace_last_error().startswith(name.encode() + b":"), lib.grace_last_error()
 
 
 def test_argument_errors_do_not_touch_the_device():
@@ -102,8 +79,8 @@ def test_argument_errors_do_not_touch_the_device():
     good = [p, 0, p, p, 1, 4, 127, 128, 0, None, 1, None, p, p, None]
     bad = [(0, None), (2, None), (3, None), (12, None), (13, None), (0, p + 1), (0, p + 2), (0, p + 4), (1, -1),
            (4, 0), (4, seg_max + 1), (5, -1), (5, 1 << 24), (6, 0), (7, 64), (7, 256), (8, 2)]
-    _check_bad(lib, name, good, bad)
-    _check_bad(lib, name, [p, 0, p, p, 1, 4, 255, 128, 1, None, 1, None, p, p, None], [(6, 255)])   # variant 1: q < 128
+    check_bad(lib, name, good, bad)
+    check_bad(lib, name, [p, 0, p, p, 1, 4, 255, 128, 1, None, 1, None, p, p, None], [(6, 255)])   # variant 1: q < 128
     good[5] = 0
     assert getattr(lib, name)(*good) == 0
 
@@ -112,7 +89,7 @@ def test_argument_errors_do_not_touch_the_device():
     good = [p, p, p, 1, 4, 127, 0, None, 1, p, None]
     bad = [(0, None), (1, None), (2, None), (9, None), (0, p + 2), (9, p + 2), (9, p + 1), (3, 0), (3, seg_max + 1),
            (4, -1), (4, 1 << 24), (5, 0), (6, 3)]
-    _check_bad(lib, name, good, bad)
+    check_bad(lib, name, good, bad)
     good[4] = 0
     assert getattr(lib, name)(*good) == 0
 
@@ -121,7 +98,7 @@ def test_argument_errors_do_not_touch_the_device():
     good = [p, p, 512, 4, 2, p, p, 1, 512, 127, 128, 0, 1, 2.0, p, None]
     bad = [(0, None), (1, None), (5, None), (6, None), (14, None), (14, p + 2), (4, 0), (4, -1), (7, 0),
            (7, seg_max + 1), (8, -1), (8, 1 << 31), (10, 64), (9, 0)]
-    _check_bad(lib, name, good, bad)
+    check_bad(lib, name, good, bad)
     good[8] = 0
     assert getattr(lib, name)(*good) == 0
 
@@ -130,43 +107,28 @@ def test_argument_errors_do_not_touch_the_device():
     good = [p, p, p, 1, 1, None, None, 1, p, p, p, None]
     bad = [(0, None), (1, None), (2, None), (8, None), (9, None), (10, None), (0, p + 2), (6, p + 8), (3, 0),
            (3, seg_max + 1), (4, 0), (4, -1), (4, (1 << 17) + 2)]
-    _check_bad(lib, name, good, bad)
+    check_bad(lib, name, good, bad)
 
     # x, seg_off, unit_off, nseg, nunits, clip_in, u, seed, scalars, ws, out, stream
     name = "grace_terngrad_step_w1_bf16"
     good = [p, p, p, 1, 1, None, None, 1, p, p, p, None]
     bad = [(0, None), (1, None), (2, None), (8, None), (9, None), (10, None), (0, p + 2), (10, p + 2), (10, p + 1),
            (6, p + 4), (3, 0), (3, seg_max + 1), (4, 0), (4, -1), (4, (1 << 17) + 2)]
-    _check_bad(lib, name, good, bad)
+    check_bad(lib, name, good, bad)
 
     # codes, scalars, code_stride, scal_stride, world, seg_off, nseg, n, aggregate, divisor, out, stream
     name = "grace_terngrad_decompress_bf16"
     good = [p, p, 512, 1, 2, p, 1, 512, 1, 2.0, p, None]
     bad = [(0, None), (1, None), (5, None), (10, None), (10, p + 2), (10, p + 4), (4, 0), (4, -2), (6, 0),
            (6, seg_max + 1), (7, -1), (7, 1 << 31)]
-    _check_bad(lib, name, good, bad)
+    check_bad(lib, name, good, bad)
     good[7] = 0
     assert getattr(lib, name)(*good) == 0
 
 
-class OnGpu(torch.Tensor):
-    """A CPU tensor that says it is on the GPU, so that the wrappers get as far as their own checks."""
-    device = property(lambda self: torch.device("cuda", 0))
-    is_cuda = property(lambda self: True)
-
-
-def _no_native(monkeypatch):
-    from grace_amd import _lib
-
-    def no_native(*a, **kw):
-        raise AssertionError("a native call was made")
-    for attr in ("call", "query", "fn", "load"):
-        monkeypatch.setattr(_lib, attr, no_native)
-
-
 def test_ops_check_dtypes_before_any_native_call(monkeypatch):
     from grace_amd import ops
-    _no_native(monkeypatch)
+    no_native(monkeypatch)
     i8, f32 = torch.zeros(256, dtype=torch.int8), torch.zeros(2)
     for dtype in (torch.float16, torch.float64, torch.int16):
         for x in (torch.zeros(256, dtype=dtype), torch.zeros(256, dtype=dtype).as_subclass(OnGpu)):
@@ -195,7 +157,7 @@ def test_ops_refuse_bf16_outside_the_fast_paths(monkeypatch):
     """bucket_size != 128, more than 512 segments, 2^24 buckets or more, 2^31 elements or more and
     a misaligned bf16 view: ValueError before any native call (CPU and `meta` tensors)."""
     from grace_amd import ops
-    _no_native(monkeypatch)
+    no_native(monkeypatch)
     x = torch.zeros(1024, dtype=torch.bfloat16)
     many = [2] * 513
     xm = torch.zeros(1026, dtype=torch.bfloat16)

@@ -2,12 +2,12 @@
 library and bound in grace_amd/_lib.py; the chunk queries return the main pass's chunk lengths of
 both element types; bad arguments are refused without touching the device (no GPU)."""
 import ctypes
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_util import header
+
 NAMES = ["grace_topk_segmented_chunk_bf16", "grace_topk_segmented_step_bf16"]
 # (has_residual, dense_out): elements per main-pass chunk
 CASES = [(1, 1), (1, 0), (0, 1), (0, 0)]
@@ -16,8 +16,7 @@ CASES = [(1, 1), (1, 0), (0, 1), (0, 0)]
 @pytest.mark.parametrize("name", NAMES)
 def test_segmented_bf16_entry_point_declared_exported_bound(name):
     from grace_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "grace_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = header("grace_hip.h")
     assert re.search(r"\b%s\s*\(" % name, hdr), "not declared in include/grace_hip.h"
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), name), "not exported by the library"
     assert name in _lib.SIGNATURES, "not bound in grace_amd/_lib.py"

@@ -2,36 +2,25 @@
 bound, mirror their f32 twins and refuse bad arguments without touching the device; the checks of
 ops.shard_select / ops.shard_clear / ops.fill_bf16 on the output's dtype need no GPU either."""
 import ctypes
-import os
 import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_util import header, no_native, params
+
 NEW = ("grace_shard_select_bf16", "grace_shard_clear_bf16", "grace_fill_bf16")
-
-
-def _header():
-    hdr = open(os.path.join(ROOT, "include", "grace_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-
-def _params(hdr, name):
-    m = re.search(r"\b%s\s*\(([^)]*)\)" % name, hdr)
-    assert m, f"{name} is not declared in include/grace_hip.h"
-    return re.sub(r"\s+", " ", m.group(1)).strip()
 
 
 def test_entry_points_declared_exported_bound():
     from grace_amd import _lib
-    hdr = _header()
+    hdr = header("grace_hip.h")
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in NEW:
-        _params(hdr, name)
+        params(hdr, name)
         assert hasattr(lib, name), f"{name} is not exported by the library"
         assert name in _lib.SIGNATURES
-    assert _params(hdr, "grace_fill_bf16") == "uint16_t* x, uint16_t bits, int64_t n, void* stream"
+    assert params(hdr, "grace_fill_bf16") == "uint16_t* x, uint16_t bits, int64_t n, void* stream"
     assert _lib.SIGNATURES["grace_fill_bf16"] == (_lib.ST, [_lib.P, ctypes.c_uint16, _lib.I64, _lib.P])
     # 156 before this change (DESIGN.md §9 "Segmented step"), three more with it
     assert len(set(re.findall(r"\b(grace_[a-z0-9_]+)\s*\(", hdr))) == 159
@@ -40,10 +29,10 @@ def test_entry_points_declared_exported_bound():
 @pytest.mark.parametrize("f32", ["grace_shard_select", "grace_shard_clear"])
 def test_bf16_twin_mirrors_the_f32_entry_point(f32):
     from grace_amd import _lib
-    hdr = _header()
-    want = _params(hdr, f32)
+    hdr = header("grace_hip.h")
+    want = params(hdr, f32)
     assert want.count("float* out") == 1
-    assert _params(hdr, f32 + "_bf16") == want.replace("float* out", "uint16_t* out")
+    assert params(hdr, f32 + "_bf16") == want.replace("float* out", "uint16_t* out")
     assert _lib.SIGNATURES[f32 + "_bf16"] == _lib.SIGNATURES[f32]
 
 
@@ -102,12 +91,8 @@ def test_fill_argument_errors_do_not_touch_the_device():
 
 
 def test_out_dtype_is_checked_before_any_native_call(monkeypatch):
-    from grace_amd import _lib, ops
-
-    def no_native(*a, **kw):
-        raise AssertionError("a native call was made")
-    monkeypatch.setattr(_lib, "call", no_native)
-    monkeypatch.setattr(_lib, "query", no_native)
+    from grace_amd import ops
+    no_native(monkeypatch)
     i32 = torch.zeros(64, dtype=torch.int32)
     i64 = torch.zeros(4, dtype=torch.int64)
     res = torch.zeros(16)

@@ -9,7 +9,8 @@ import re
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_util import ROOT, OnGpu, check_bad, declared, header, no_native, params
+
 NEW = ("grace_efsign_workspace_bytes", "grace_efsign_step", "grace_efsign_step_bf16",
        "grace_efsign_decode_aggregate", "grace_efsign_decode_aggregate_bf16", "grace_sign_encode_bf16",
        "grace_sign_encode_bits_bf16", "grace_sign_step_w1_bf16", "grace_sign_majority_bf16",
@@ -27,26 +28,11 @@ TWINS = {
 }
 
 
-def _header(name):
-    hdr = open(os.path.join(ROOT, "include", name)).read()
-    return re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-
-def _declared(hdr):
-    return sorted(set(re.findall(r"\b(grace_[a-z0-9_]+)\s*\(", hdr)))
-
-
-def _params(hdr, name):
-    m = re.search(r"\b%s\s*\(([^)]*)\)" % name, hdr)
-    assert m, f"{name} is not declared"
-    return re.sub(r"\s+", " ", m.group(1)).strip()
-
-
 def test_entry_points_declared_exported_bound():
     from grace_amd import _lib
-    sign = _header("grace_hip_sign.h")
+    sign = header("grace_hip_sign.h")
     assert '#include "grace_hip.h"' in sign and 'extern "C"' in sign
-    assert _declared(sign) == sorted(NEW) == sorted(_lib.SIGNATURES_SIGN)
+    assert declared(sign) == sorted(NEW) == sorted(_lib.SIGNATURES_SIGN)
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in NEW:
         assert hasattr(lib, name), f"{name} is not exported by the library"
@@ -54,7 +40,7 @@ def test_entry_points_declared_exported_bound():
     for name, (res, args) in _lib.SIGNATURES_SIGN.items():
         f = getattr(bound, name)
         assert f.restype == res and list(f.argtypes) == args, name
-        assert len(args) == _params(sign, name).count(",") + 1, name
+        assert len(args) == params(sign, name).count(",") + 1, name
     # every entry point of the new header has a doc comment right above it
     raw = open(os.path.join(ROOT, "include", "grace_hip_sign.h")).read()
     for name in NEW:
@@ -63,7 +49,7 @@ def test_entry_points_declared_exported_bound():
 
 def test_first_header_and_table_are_unchanged():
     from grace_amd import _lib
-    names = _declared(_header("grace_hip.h"))
+    names = declared(header("grace_hip.h"))
     assert len(names) == 159 and len(_lib.SIGNATURES) == 159 and sorted(_lib.SIGNATURES) == names
     assert not set(NEW) & set(names) and not set(NEW) & set(_lib.SIGNATURES)
 
@@ -72,22 +58,13 @@ def test_first_header_and_table_are_unchanged():
 def test_bf16_twin_mirrors_the_f32_entry_point(f32):
     from grace_amd import _lib
     where, subs = TWINS[f32]
-    want = _params(_header(where), f32)
+    want = params(header(where), f32)
     for s in subs:
         assert want.count(s) == 1, (f32, s)
         want = want.replace(s, s.replace("float*", "uint16_t*"))
-    assert _params(_header("grace_hip_sign.h"), f32 + "_bf16") == want
+    assert params(header("grace_hip_sign.h"), f32 + "_bf16") == want
     table = _lib.SIGNATURES if where == "grace_hip.h" else _lib.SIGNATURES_SIGN
     assert _lib.SIGNATURES_SIGN[f32 + "_bf16"] == table[f32]
-
-
-def _check_bad(lib, name, good, bad):
-    f = getattr(lib, name)
-    for i, v in bad:
-        args = list(good)
-        args[i] = v
-        assert f(*args) == -1, (name, i, v)
-        assert lib.grace_last_error().startswith(name.encode() + b":"), lib.grace_last_error()
 
 
 @pytest.mark.parametrize("bf16", [False, True])
@@ -108,13 +85,13 @@ def test_argument_errors_do_not_touch_the_device(bf16):
     good = [p, p, 1, 0.1, 8, p, None, None, 0.1, p, ws, None]
     bad = [(0, None), (1, None), (5, None), (9, None), (4, -1), (10, ws - 1), (10, 0)]
     bad += [(0, a) for a in odd] + [(7, a) for a in odd]
-    _check_bad(lib, name, good, bad)
+    check_bad(lib, name, good, bad)
     good[4] = 0
     assert getattr(lib, name)(*good) == 0
 
     name = "grace_efsign_decode_aggregate" + sfx      # means, codes_wn, world, lr_agg, out, n, stream
     good = [p, p, 2, 0.1, p, 8, None]
-    _check_bad(lib, name, good, [(0, None), (1, None), (4, None), (2, 0), (2, -3), (5, -1)] + [(4, a) for a in odd])
+    check_bad(lib, name, good, [(0, None), (1, None), (4, None), (2, 0), (2, -3), (5, -1)] + [(4, a) for a in odd])
     good[5] = 0
     assert getattr(lib, name)(*good) == 0
 
@@ -131,23 +108,14 @@ def test_argument_errors_do_not_touch_the_device(bf16):
                                      [(0, None), (1, None), (5, None), (6, -1), (0, p + 1)], 6),
     }
     for name, (good, bad, n_at) in cases.items():
-        _check_bad(lib, name, good, bad)
+        check_bad(lib, name, good, bad)
         good[n_at] = 0
         assert getattr(lib, name)(*good) == 0, name
 
 
 def test_ops_check_dtypes_before_any_native_call(monkeypatch):
-    from grace_amd import _lib, ops
-
-    def no_native(*a, **kw):
-        raise AssertionError("a native call was made")
-    for attr in ("call", "query", "fn", "load"):
-        monkeypatch.setattr(_lib, attr, no_native)
-    class OnGpu(torch.Tensor):
-        """A CPU tensor that says it is on the GPU, so that the wrappers get as far as the dtype."""
-        device = property(lambda self: torch.device("cuda", 0))
-        is_cuda = property(lambda self: True)
-
+    from grace_amd import ops
+    no_native(monkeypatch)
     u8 = torch.zeros(64, dtype=torch.uint8)
     for dtype in (torch.float16, torch.float64, torch.int16):
         x = torch.zeros(64, dtype=dtype).as_subclass(OnGpu)
@@ -175,12 +143,8 @@ def test_ops_check_dtypes_before_any_native_call(monkeypatch):
 def test_ops_check_shapes_before_any_native_call(monkeypatch):
     """efsign_step's residual and out, signum_encode's momentum on bf16, and the decode's payload
     sizes: checked on `meta` tensors, which have a device type of their own and no memory."""
-    from grace_amd import _lib, ops
-
-    def no_native(*a, **kw):
-        raise AssertionError("a native call was made")
-    for attr in ("call", "query", "fn", "load"):
-        monkeypatch.setattr(_lib, attr, no_native)
+    from grace_amd import ops
+    no_native(monkeypatch)
     monkeypatch.setattr(ops, "dev_grad", lambda t, what="gradient": t)   # as if the tensors were on the GPU
     monkeypatch.setattr(ops, "require_dev", lambda t, what="tensor": t)
     g = torch.zeros(64, dtype=torch.bfloat16)

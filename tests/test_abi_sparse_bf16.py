@@ -8,57 +8,36 @@ import ctypes
 import inspect
 import os
 import re
-import textwrap
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import grace_oracle as O
+from tests.abi_util import ROOT, OnGpu, body, check_bad, check_types, declared, header, no_native, params
 from tests.golden_util import same_bits
 from tests.sparse_bf16_util import padded_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 NEW = ("grace_axpby_bf16", "grace_randomk_aggregate_bf16", "grace_randomk_clear", "grace_randomk_step_w1_dense_bf16",
        "grace_sparse_aggregate_padded_bf16", "grace_sparse_aggregate_padded_bf16_workspace_bytes",
        "grace_threshold_step_w1_bf16")
 
 
-def _header(name):
-    hdr = open(os.path.join(ROOT, "include", name)).read()
-    return re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-
-
-def _declared(hdr):
-    return sorted(set(re.findall(r"\b(grace_[a-z0-9_]+)\s*\(", hdr)))
-
-
-def _params(hdr, name):
-    m = re.search(r"\b%s\s*\(([^)]*)\)" % name, hdr)
-    assert m, f"{name} is not declared"
-    return re.sub(r"\s+", " ", m.group(1)).strip()
-
-
 def test_entry_points_declared_exported_bound():
     from grace_amd import _lib
-    hdr = _header("grace_hip_sparse.h")
+    hdr = header("grace_hip_sparse.h")
     assert '#include "grace_hip.h"' in hdr and 'extern "C"' in hdr
-    assert _declared(hdr) == sorted(NEW) == sorted(_lib.SIGNATURES_SPARSE)
+    assert declared(hdr) == sorted(NEW) == sorted(_lib.SIGNATURES_SPARSE)
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in NEW:
         assert hasattr(lib, name), f"{name} is not exported by the library"
     bound = _lib.load()
-    ctype_of = {"float": _lib.F32, "int32_t": _lib.I32, "int64_t": _lib.I64, "size_t": _lib.SZ}
     for name, (res, args) in _lib.SIGNATURES_SPARSE.items():
         f = getattr(bound, name)
         assert f.restype == res and list(f.argtypes) == args, name
-        params = [p.strip() for p in _params(hdr, name).split(",")]
-        assert len(args) == len(params), name
-        for p, a in zip(params, args):      # each bound type is the prototype's
-            want = _lib.P if "*" in p else ctype_of[p.rsplit(" ", 1)[0]]
-            assert a is want, (name, p)
         assert res is (_lib.SZ if name.endswith("_bytes") else _lib.ST)
+    check_types(hdr, _lib.SIGNATURES_SPARSE)      # each bound type is the prototype's
     raw = open(os.path.join(ROOT, "include", "grace_hip_sparse.h")).read()
     for name in NEW:   # a doc comment right above every entry point
         assert re.search(r"\*/\s*\n[a-z_ ]+\b%s\(" % name, raw), f"{name} has no doc comment"
@@ -66,37 +45,28 @@ def test_entry_points_declared_exported_bound():
 
 def test_first_four_headers_and_tables_are_unchanged():
     from grace_amd import _lib
-    for header, table, count in (("grace_hip.h", _lib.SIGNATURES, 159), ("grace_hip_sign.h", _lib.SIGNATURES_SIGN, 11),
-                                 ("grace_hip_quant.h", _lib.SIGNATURES_QUANT, 6),
-                                 ("grace_hip_dgc.h", _lib.SIGNATURES_DGC, 8)):
-        names = _declared(_header(header))
-        assert len(names) == count and len(table) == count and sorted(table) == names, header
+    for h, table, count in (("grace_hip.h", _lib.SIGNATURES, 159), ("grace_hip_sign.h", _lib.SIGNATURES_SIGN, 11),
+                            ("grace_hip_quant.h", _lib.SIGNATURES_QUANT, 6),
+                            ("grace_hip_dgc.h", _lib.SIGNATURES_DGC, 8)):
+        names = declared(header(h))
+        assert len(names) == count and len(table) == count and sorted(table) == names, h
         assert not set(NEW) & set(names)
 
 
 def test_threshold_twin_mirrors_the_f32_entry_point():
     from grace_amd import _lib
-    want = _params(_header("grace_hip.h"), "grace_threshold_step_w1")
+    want = params(header("grace_hip.h"), "grace_threshold_step_w1")
     for s in ("const float* g", "float* out"):
         assert want.count(s) == 1, s
         want = want.replace(s, s.replace("float*", "uint16_t*"))
-    assert _params(_header("grace_hip_sparse.h"), "grace_threshold_step_w1_bf16") == want
+    assert params(header("grace_hip_sparse.h"), "grace_threshold_step_w1_bf16") == want
     assert _lib.SIGNATURES_SPARSE["grace_threshold_step_w1_bf16"] == _lib.SIGNATURES["grace_threshold_step_w1"]
     # the dense random-k twin drops the recycled output's two grouping buffers and nothing else
-    f32 = _params(_header("grace_hip.h"), "grace_randomk_step_w1_dense")
+    f32 = params(header("grace_hip.h"), "grace_randomk_step_w1_dense")
     for s in ("const float* g", "float* out"):
         f32 = f32.replace(s, s.replace("float*", "uint16_t*"))
     f32 = f32.replace(" void* grp, const void* prev_grp,", "")
-    assert _params(_header("grace_hip_sparse.h"), "grace_randomk_step_w1_dense_bf16") == f32
-
-
-def _check_bad(lib, name, good, bad):
-    f = getattr(lib, name)
-    for i, v in bad:
-        args = list(good)
-        args[i] = v
-        assert f(*args) == -1, (name, i, v)
-        assert lib.grace_last_error().startswith(name.encode() + b":"), lib.grace_last_error()
+    assert params(header("grace_hip_sparse.h"), "grace_randomk_step_w1_dense_bf16") == f32
 
 
 def test_argument_errors_do_not_touch_the_device():
@@ -110,32 +80,32 @@ def test_argument_errors_do_not_touch_the_device():
 
     # g, residual, mode, beta, gamma, n, thr, ws, out, stream
     good = [p, q, 2, 0.9, 0.7, 16, 1.5, r, s, None]
-    _check_bad(lib, "grace_threshold_step_w1_bf16", good,
-               [(0, None), (1, None), (7, None), (8, None), (2, -1), (2, 3), (5, 0), (5, -1)])
+    check_bad(lib, "grace_threshold_step_w1_bf16", good,
+              [(0, None), (1, None), (7, None), (8, None), (2, -1), (2, 3), (5, 0), (5, -1)])
 
     # r, g, has_residual, beta, gamma, t, n, stream
     good = [p, q, 1, 0.9, 0.7, r, 16, None]
-    _check_bad(lib, "grace_axpby_bf16", good, [(0, None), (1, None), (5, None), (6, -1)])
+    check_bad(lib, "grace_axpby_bf16", good, [(0, None), (1, None), (5, None), (6, -1)])
     good[6] = 0
     assert lib.grace_axpby_bf16(*good) == 0
 
     # g, residual, has_residual, beta, gamma, n, idx, k, out, ws, ws_bytes, stream
     need = lib.grace_randomk_step_w1_dense_workspace_bytes(16, 4)
     good = [p, q, 1, 0.9, 0.7, 16, r, 4, s, p, need, None]
-    _check_bad(lib, "grace_randomk_step_w1_dense_bf16", good,
-               [(0, None), (1, None), (6, None), (8, None), (9, None), (5, 0), (5, -1), (5, (1 << 28) + 1), (7, -1),
-                (10, need - 1)])
+    check_bad(lib, "grace_randomk_step_w1_dense_bf16", good,
+              [(0, None), (1, None), (6, None), (8, None), (9, None), (5, 0), (5, -1), (5, (1 << 28) + 1), (7, -1),
+               (10, need - 1)])
 
     # idx, vals, k, r, n, stream
     good = [p, q, 4, r, 16, None]
-    _check_bad(lib, "grace_randomk_clear", good, [(0, None), (1, None), (3, None), (2, -1), (4, 0)])
+    check_bad(lib, "grace_randomk_clear", good, [(0, None), (1, None), (3, None), (2, -1), (4, 0)])
     good[2] = 0
     assert lib.grace_randomk_clear(*good) == 0
 
     # vals, idx, k, world, divisor, out, n, stream
     good = [p, q, 4, 2, 2.0, r, 16, None]
-    _check_bad(lib, "grace_randomk_aggregate_bf16", good,
-               [(0, None), (1, None), (5, None), (2, -1), (3, 0), (3, -1), (6, 0), (6, -1)])
+    check_bad(lib, "grace_randomk_aggregate_bf16", good,
+              [(0, None), (1, None), (5, None), (2, -1), (3, 0), (3, -1), (6, 0), (6, -1)])
 
     # base, cap, counts, world, divisor, out, n, ws, ws_bytes, stream
     wsb = lib.grace_sparse_aggregate_padded_bf16_workspace_bytes
@@ -144,27 +114,12 @@ def test_argument_errors_do_not_touch_the_device():
     good = [p, 8, q, 2, 2.0, r, 100, s, wsb(2, 100), None]
     bad = [(0, None), (2, None), (5, None), (7, None), (1, 0), (1, -1), (1, 101), (3, 0), (3, -1), (3, 1025), (6, 0),
            (6, 7), (6, 1 << 31), (8, 0), (8, wsb(2, 100) - 1)]
-    _check_bad(lib, "grace_sparse_aggregate_padded_bf16", good, bad)
-
-
-class OnGpu(torch.Tensor):
-    """A CPU tensor that says it is on the GPU, so that the wrappers get as far as their own checks."""
-    device = property(lambda self: torch.device("cuda", 0))
-    is_cuda = property(lambda self: True)
-
-
-def _no_native(monkeypatch):
-    from grace_amd import _lib
-
-    def no_native(*a, **kw):
-        raise AssertionError("a native call was made")
-    for attr in ("call", "query", "fn", "load"):
-        monkeypatch.setattr(_lib, attr, no_native)
+    check_bad(lib, "grace_sparse_aggregate_padded_bf16", good, bad)
 
 
 def test_ops_check_dtypes_and_limits_before_any_native_call(monkeypatch):
     from grace_amd import ops
-    _no_native(monkeypatch)
+    no_native(monkeypatch)
     f32 = torch.zeros(256).as_subclass(OnGpu)
     bf = torch.zeros(256, dtype=torch.bfloat16).as_subclass(OnGpu)
     idx = torch.zeros(4, dtype=torch.int64).as_subclass(OnGpu)
@@ -220,18 +175,12 @@ def test_classes_are_the_dist_classes():
     assert (k.compress_ratio, k.rng, k.recycle_output, k.global_step) == (0.25, "torch_cpu", False, 0)
 
 
-def _body(fn):
-    src = textwrap.dedent(inspect.getsource(fn))
-    src = re.sub(r'""".*?"""', "", src, count=1, flags=re.S)     # the docstring
-    return [ln.rstrip() for ln in src.split("\n")[1:] if ln.strip()]  # without the def line
-
-
 def test_counts_exchange_is_the_parents_but_for_the_decode():
     """grace_amd/dist/ has no hook at the decode, so the stand-in repeats _counts_exchange: its body is
     the parent's text with the two f32 decode calls replaced by the padded bf16 decode, nothing else."""
     from grace_amd import sparse_bf16 as S
     from grace_amd.dist.compressor.threshold import ThresholdCompressor
-    parent, ours = _body(ThresholdCompressor._counts_exchange), _body(S.ThresholdCompressor._counts_exchange_bf16)
+    parent, ours = body(ThresholdCompressor._counts_exchange), body(S.ThresholdCompressor._counts_exchange_bf16)
     at = [i for i, ln in enumerate(parent) if "ops.sparse_aggregate(" in ln]
     assert len(at) == 2 and parent[at[0] + 1].strip() == "W if self.average else 1)"
     want = list(parent)
@@ -248,7 +197,7 @@ def test_exchange_step_is_the_parents_fused_step_from_its_count_on():
     its end, with the counts exchange renamed and `out_dtype=BF16` added to the records decode."""
     from grace_amd import sparse_bf16 as S
     from grace_amd.dist.compressor.threshold import ThresholdCompressor
-    parent, ours = _body(ThresholdCompressor.fused_step), _body(S.ThresholdCompressor._exchange_step)
+    parent, ours = body(ThresholdCompressor.fused_step), body(S.ThresholdCompressor._exchange_step)
     starts = [i for i, ln in enumerate(parent) if ln.strip().startswith('ws = ops.workspace("threshold"')]
     assert len(starts) == 2                                   # the world-1 fused pass, then the exchange part
     tail = parent[starts[1]:]
@@ -285,7 +234,7 @@ def test_limits_raise_value_error_before_anything_runs(monkeypatch):
     from grace_amd import sparse_bf16 as S
     from grace_amd.dist.communicator.allgather import Allgather
     from grace_amd.dist.memory.residual import ResidualMemory
-    _no_native(monkeypatch)
+    no_native(monkeypatch)
 
     class Big(OnGpu):
         size = 1 << 31

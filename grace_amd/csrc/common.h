@@ -55,6 +55,14 @@ inline unsigned stream_grid(int64_t n_vec, int block, int64_t cap = 2048) {
   return (unsigned)g;
 }
 
+// Launch-side alignment tests: is p a multiple of 2 / 4 / 8 / 16 bytes (a null pointer counts as
+// aligned: an absent operand never forbids the vector path), and a workspace size rounded up to 256 B.
+inline bool al2(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1u) == 0; }
+inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
 // ------------------------------------------------------------------------------------------------
 // device helpers
 __device__ __forceinline__ uint32_t f2u(float x) { return __float_as_uint(x); }

@@ -105,8 +105,6 @@ struct DgcWs {
   uint32_t* offs;     // [nchunks] exclusive offsets
 };
 
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static DgcWs dgc_carve(void* ws, int64_t n) {
   const int64_t nch = (n + kDChunk - 1) / kDChunk;
   char* p = reinterpret_cast<char*>(ws);
@@ -919,6 +917,70 @@ static grace_status_t dgc_step_w1_fused_any(const char* name, const char* bad, c
   return GRACE_OK;
 }
 
+// the table, the counts against it and the replay of the reference's loop: all of grace_dgc_select, and
+// what grace_dgc_threshold begins with
+static grace_status_t dgc_select(const char* name, const float* t, int64_t n, const float* top_vals, int64_t ks,
+                                 double ratio, const DgcWs& w, hipStream_t s) {
+  dgc_table_kernel<<<1, 1024, 0, s>>>(top_vals, ks, w);
+  GRACE_CHECK_LAUNCH(name);
+  dgc_count_kernel<false><<<stream_grid((n + 3) / 4, kDBlock, 2048), kDBlock, 0, s>>>(t, n, w);
+  GRACE_CHECK_LAUNCH(name);
+  dgc_replay_kernel<false><<<1, 64, 0, s>>>(n, ratio, w);
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
+
+// the launches of a float entry point and its bfloat16 twin (T = uint16_t), which checks its own arguments
+template <typename T>
+static grace_status_t dgc_sample_comp(const char* name, const T* g, const float* residual, const float* accum,
+                                      int32_t has_state, float momentum, int64_t n, const int64_t* sample_idx,
+                                      uint64_t seed, int64_t ns, float* sample_abs, void* stream) {
+  dgc_sample_comp_kernel<T><<<stream_grid(ns, kDBlock, 1024), kDBlock, 0, as_stream(stream)>>>(
+      g, residual, accum, has_state, momentum, n, sample_idx, seed, ns, sample_abs);
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
+
+template <typename T>
+static grace_status_t dgc_compensate(const char* name, const T* g, float* residual, float* accum, int32_t has_state,
+                                     float momentum, int64_t n, void* stream) {
+  if (n == 0) return GRACE_OK;
+  dgc_compensate_kernel<false, T><<<stream_grid((n + 3) / 4, kDBlock * kDQ, 4096), kDBlock, 0, as_stream(stream)>>>(
+      g, residual, accum, has_state, momentum, n, residual, accum, nullptr);
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
+
+template <typename T>
+static grace_status_t dgc_mask_out(const char* name, const float* t, float* residual, float* accum, int64_t n,
+                                   const void* ws, T* out, void* stream) {
+  if (n == 0) return GRACE_OK;
+  dgc_mask_kernel<true, false, T><<<stream_grid((n + 3) / 4, kDBlock * kDQ, 4096), kDBlock, 0, as_stream(stream)>>>(
+      t, residual, accum, n, reinterpret_cast<const DgcMeta*>(ws), out);
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
+
+template <typename T>
+static grace_status_t sumsq(const char* name, const T* x, int64_t n, void* ws, float* out, void* stream) {
+  const unsigned nb = n ? stream_grid(n, kDBlock, 1024) : 1;   // one grid for both types: the same partial sums
+  hipStream_t s = as_stream(stream);
+  sumsq_kernel<T><<<nb, kDBlock, 0, s>>>(x, n, reinterpret_cast<double*>(ws));
+  GRACE_CHECK_LAUNCH(name);
+  sumsq_finish_kernel<<<1, 64, 0, s>>>(reinterpret_cast<const double*>(ws), (int)nb, out);
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
+
+template <typename T>
+static grace_status_t clip_by_sumsq(const char* name, const T* x, const float* sumsq_dev, float world, float* out,
+                                    int64_t n, void* stream) {
+  if (n == 0) return GRACE_OK;
+  clip_kernel<T><<<stream_grid(n, kDBlock, 2048), kDBlock, 0, as_stream(stream)>>>(x, sumsq_dev, world, out, n);
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
+
 extern "C" {
 
 size_t grace_dgc_workspace_bytes(int64_t n) { return dgc_ws_bytes(n < 1 ? 1 : n); }
@@ -938,12 +1000,8 @@ grace_status_t grace_dgc_threshold(const float* t, int64_t n, const float* top_v
   hipStream_t s = as_stream(stream);
   DgcWs w = dgc_carve(ws, n);
   const int64_t nch = (n + kDChunk - 1) / kDChunk;
-  dgc_table_kernel<<<1, 1024, 0, s>>>(top_vals, ks, w);
-  GRACE_CHECK_LAUNCH("grace_dgc_threshold");
-  dgc_count_kernel<false><<<stream_grid((n + 3) / 4, kDBlock, 2048), kDBlock, 0, s>>>(t, n, w);
-  GRACE_CHECK_LAUNCH("grace_dgc_threshold");
-  dgc_replay_kernel<false><<<1, 64, 0, s>>>(n, ratio, w);
-  GRACE_CHECK_LAUNCH("grace_dgc_threshold");
+  const grace_status_t st = dgc_select("grace_dgc_threshold", t, n, top_vals, ks, ratio, w, s);
+  if (st != GRACE_OK) return st;
   dgc_chunk_kernel<<<(unsigned)nch, kDBlock, 0, s>>>(t, n, w);
   GRACE_CHECK_LAUNCH("grace_dgc_threshold");
   dgc_offsets_kernel<<<1, 1024, 0, s>>>(nch, w);
@@ -984,11 +1042,7 @@ grace_status_t grace_dgc_mask_update_capped(const uint32_t* rec, int64_t cap, fl
 grace_status_t grace_dgc_compensate(const float* g, float* residual, float* accum, int32_t has_state,
                                     float momentum, int64_t n, void* stream) {
   GRACE_REQUIRE(g && residual && accum && n >= 0, "grace_dgc_compensate: bad arguments");
-  if (n == 0) return GRACE_OK;
-  dgc_compensate_kernel<false><<<stream_grid((n + 3) / 4, kDBlock * kDQ, 4096), kDBlock, 0, as_stream(stream)>>>(
-      g, residual, accum, has_state, momentum, n, residual, accum, nullptr);
-  GRACE_CHECK_LAUNCH("grace_dgc_compensate");
-  return GRACE_OK;
+  return dgc_compensate<float>("grace_dgc_compensate", g, residual, accum, has_state, momentum, n, stream);
 }
 
 grace_status_t grace_dgc_mask_update(const float* t, float* residual, float* accum, int64_t n, const void* ws,
@@ -1004,25 +1058,13 @@ grace_status_t grace_dgc_mask_update(const float* t, float* residual, float* acc
 grace_status_t grace_dgc_select(const float* t, int64_t n, const float* top_vals, int64_t ks, double ratio, void* ws,
                                 void* stream) {
   GRACE_REQUIRE(t && top_vals && ws && n >= 1 && ks >= 1, "grace_dgc_select: bad arguments");
-  hipStream_t s = as_stream(stream);
-  DgcWs w = dgc_carve(ws, n);
-  dgc_table_kernel<<<1, 1024, 0, s>>>(top_vals, ks, w);
-  GRACE_CHECK_LAUNCH("grace_dgc_select");
-  dgc_count_kernel<false><<<stream_grid((n + 3) / 4, kDBlock, 2048), kDBlock, 0, s>>>(t, n, w);
-  GRACE_CHECK_LAUNCH("grace_dgc_select");
-  dgc_replay_kernel<false><<<1, 64, 0, s>>>(n, ratio, w);
-  GRACE_CHECK_LAUNCH("grace_dgc_select");
-  return GRACE_OK;
+  return dgc_select("grace_dgc_select", t, n, top_vals, ks, ratio, dgc_carve(ws, n), as_stream(stream));
 }
 
 grace_status_t grace_dgc_step_w1(const float* t, float* residual, float* accum, int64_t n, const void* ws, float* out,
                                  void* stream) {
   GRACE_REQUIRE(t && residual && accum && ws && out && n >= 0, "grace_dgc_step_w1: bad arguments");
-  if (n == 0) return GRACE_OK;
-  dgc_mask_kernel<true><<<stream_grid((n + 3) / 4, kDBlock * kDQ, 4096), kDBlock, 0, as_stream(stream)>>>(
-      t, residual, accum, n, reinterpret_cast<const DgcMeta*>(ws), out);
-  GRACE_CHECK_LAUNCH("grace_dgc_step_w1");
-  return GRACE_OK;
+  return dgc_mask_out<float>("grace_dgc_step_w1", t, residual, accum, n, ws, out, stream);
 }
 
 grace_status_t grace_dgc_sample_comp(const float* g, const float* residual, const float* accum, int32_t has_state,
@@ -1030,10 +1072,8 @@ grace_status_t grace_dgc_sample_comp(const float* g, const float* residual, cons
                                      float* sample_abs, void* stream) {
   GRACE_REQUIRE(g && sample_abs && n >= 1 && ns >= 1 && (!has_state || (residual && accum)),
                 "grace_dgc_sample_comp: bad arguments");
-  dgc_sample_comp_kernel<<<stream_grid(ns, kDBlock, 1024), kDBlock, 0, as_stream(stream)>>>(
-      g, residual, accum, has_state, momentum, n, sample_idx, seed, ns, sample_abs);
-  GRACE_CHECK_LAUNCH("grace_dgc_sample_comp");
-  return GRACE_OK;
+  return dgc_sample_comp<float>("grace_dgc_sample_comp", g, residual, accum, has_state, momentum, n, sample_idx, seed,
+                                ns, sample_abs, stream);
 }
 
 size_t grace_dgc_sample_kth_workspace_bytes(void) { return al256(sizeof(KthState)); }
@@ -1078,80 +1118,52 @@ grace_status_t grace_dgc_step_w1_fused_bf16(const uint16_t* g, const float* resi
                                          accum_out, out, stream);
 }
 
+// (the bf16 twins stay below the float entry points, in this order: kernels are emitted in the order in
+// which entry points first name an instantiation -- DESIGN.md section 1, host-side convention)
 grace_status_t grace_dgc_sample_comp_bf16(const uint16_t* g, const float* residual, const float* accum,
                                           int32_t has_state, float momentum, int64_t n, const int64_t* sample_idx,
                                           uint64_t seed, int64_t ns, float* sample_abs, void* stream) {
   GRACE_REQUIRE(g && sample_abs && n >= 1 && ns >= 1 && (!has_state || (residual && accum)),
                 "grace_dgc_sample_comp_bf16: bad arguments");
-  dgc_sample_comp_kernel<uint16_t><<<stream_grid(ns, kDBlock, 1024), kDBlock, 0, as_stream(stream)>>>(
-      g, residual, accum, has_state, momentum, n, sample_idx, seed, ns, sample_abs);
-  GRACE_CHECK_LAUNCH("grace_dgc_sample_comp_bf16");
-  return GRACE_OK;
+  return dgc_sample_comp<uint16_t>("grace_dgc_sample_comp_bf16", g, residual, accum, has_state, momentum, n,
+                                   sample_idx, seed, ns, sample_abs, stream);
 }
 
 grace_status_t grace_dgc_compensate_bf16(const uint16_t* g, float* residual, float* accum, int32_t has_state,
                                          float momentum, int64_t n, void* stream) {
   GRACE_REQUIRE(g && residual && accum && residual != accum && n >= 0, "grace_dgc_compensate_bf16: bad arguments");
-  if (n == 0) return GRACE_OK;
-  dgc_compensate_kernel<false, uint16_t>
-      <<<stream_grid((n + 3) / 4, kDBlock * kDQ, 4096), kDBlock, 0, as_stream(stream)>>>(
-          g, residual, accum, has_state, momentum, n, residual, accum, nullptr);
-  GRACE_CHECK_LAUNCH("grace_dgc_compensate_bf16");
-  return GRACE_OK;
+  return dgc_compensate<uint16_t>("grace_dgc_compensate_bf16", g, residual, accum, has_state, momentum, n, stream);
 }
 
 grace_status_t grace_dgc_step_w1_bf16(const float* t, float* residual, float* accum, int64_t n, const void* ws,
                                       uint16_t* out, void* stream) {
   GRACE_REQUIRE(t && residual && accum && residual != accum && ws && out && n >= 0,
                 "grace_dgc_step_w1_bf16: bad arguments");
-  if (n == 0) return GRACE_OK;
-  dgc_mask_kernel<true, false, uint16_t>
-      <<<stream_grid((n + 3) / 4, kDBlock * kDQ, 4096), kDBlock, 0, as_stream(stream)>>>(
-          t, residual, accum, n, reinterpret_cast<const DgcMeta*>(ws), out);
-  GRACE_CHECK_LAUNCH("grace_dgc_step_w1_bf16");
-  return GRACE_OK;
+  return dgc_mask_out<uint16_t>("grace_dgc_step_w1_bf16", t, residual, accum, n, ws, out, stream);
 }
 
 size_t grace_sumsq_workspace_bytes(void) { return sizeof(double) * 1024; }
 
 grace_status_t grace_sumsq(const float* x, int64_t n, void* ws, float* out, void* stream) {
   GRACE_REQUIRE(x && ws && out && n >= 0, "grace_sumsq: bad arguments");
-  const unsigned nb = n ? stream_grid(n, kDBlock, 1024) : 1;
-  hipStream_t s = as_stream(stream);
-  sumsq_kernel<<<nb, kDBlock, 0, s>>>(x, n, reinterpret_cast<double*>(ws));
-  GRACE_CHECK_LAUNCH("grace_sumsq");
-  sumsq_finish_kernel<<<1, 64, 0, s>>>(reinterpret_cast<const double*>(ws), (int)nb, out);
-  GRACE_CHECK_LAUNCH("grace_sumsq");
-  return GRACE_OK;
+  return sumsq<float>("grace_sumsq", x, n, ws, out, stream);
 }
 
 grace_status_t grace_clip_by_sumsq(const float* x, const float* sumsq_dev, float world, float* out, int64_t n,
                                    void* stream) {
   GRACE_REQUIRE(x && sumsq_dev && out && n >= 0 && world > 0.f, "grace_clip_by_sumsq: bad arguments");
-  if (n == 0) return GRACE_OK;
-  clip_kernel<<<stream_grid(n, kDBlock, 2048), kDBlock, 0, as_stream(stream)>>>(x, sumsq_dev, world, out, n);
-  GRACE_CHECK_LAUNCH("grace_clip_by_sumsq");
-  return GRACE_OK;
+  return clip_by_sumsq<float>("grace_clip_by_sumsq", x, sumsq_dev, world, out, n, stream);
 }
 
 grace_status_t grace_sumsq_bf16(const uint16_t* x, int64_t n, void* ws, float* out, void* stream) {
   GRACE_REQUIRE(x && ws && out && n >= 0, "grace_sumsq_bf16: bad arguments");
-  const unsigned nb = n ? stream_grid(n, kDBlock, 1024) : 1;   // grace_sumsq's grid: the same partial sums
-  hipStream_t s = as_stream(stream);
-  sumsq_kernel<uint16_t><<<nb, kDBlock, 0, s>>>(x, n, reinterpret_cast<double*>(ws));
-  GRACE_CHECK_LAUNCH("grace_sumsq_bf16");
-  sumsq_finish_kernel<<<1, 64, 0, s>>>(reinterpret_cast<const double*>(ws), (int)nb, out);
-  GRACE_CHECK_LAUNCH("grace_sumsq_bf16");
-  return GRACE_OK;
+  return sumsq<uint16_t>("grace_sumsq_bf16", x, n, ws, out, stream);
 }
 
 grace_status_t grace_clip_by_sumsq_bf16(const uint16_t* x, const float* sumsq_dev, float world, float* out, int64_t n,
                                         void* stream) {
   GRACE_REQUIRE(x && sumsq_dev && out && n >= 0 && world > 0.f, "grace_clip_by_sumsq_bf16: bad arguments");
-  if (n == 0) return GRACE_OK;
-  clip_kernel<uint16_t><<<stream_grid(n, kDBlock, 2048), kDBlock, 0, as_stream(stream)>>>(x, sumsq_dev, world, out, n);
-  GRACE_CHECK_LAUNCH("grace_clip_by_sumsq_bf16");
-  return GRACE_OK;
+  return clip_by_sumsq<uint16_t>("grace_clip_by_sumsq_bf16", x, sumsq_dev, world, out, n, stream);
 }
 
 }  // extern "C"

@@ -1705,15 +1705,13 @@ static int64_t qt4_slab(int64_t n, int64_t m) {
   return slab;
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 size_t grace_powersgd_workspace_bytes(int64_t n, int64_t m, int32_t r) {
   const size_t pp = sizeof(float) * (size_t)p_ksplit(n, m, Tile<1>::C) * n * r;   // >= the R4 split
   // the larger of the two Qt kernels' slab partials (the rank-4 kernel needs 16-B aligned M and P)
   int64_t nslab = (n + qt_slab(n, m) - 1) / qt_slab(n, m);
   if (r == 4 && qt4_ok(m)) nslab = max(nslab, (n + qt4_slab(n, m) - 1) / qt4_slab(n, m));
   const size_t qp = sizeof(float) * (size_t)(nslab + (nslab + kFan - 1) / kFan) * m * r;
-  return kTicketBytes + align256(pp > qp ? pp : qp);
+  return kTicketBytes + al256(pp > qp ? pp : qp);
 }
 
 extern "C++" template <bool DRAWQ>

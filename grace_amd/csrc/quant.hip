@@ -2059,11 +2059,141 @@ __global__ __launch_bounds__(kQBlock) void qsgd_global_encode_kernel(const float
 
 using namespace grace;
 
+// ------------------------------------------------------------------------------------------------
+// Launchers: an entry point checks its arguments and returns early on an empty
+// input; a launcher typed on the gradient (XT) or the dense result (OT) -- float, or uint16_t for
+// bfloat16 -- does the rest for the float entry point and its bf16 twin alike.
+
 // the pipelined encoder's grid: the cap, or more workgroups when a workgroup's bucket range would
 // outgrow its LDS table (block_range32 rounds a range up to a multiple of 16 rows)
 static unsigned qenc_pipe_grid(int64_t nbuckets) {
   const int64_t need = (nbuckets + (kQBkMax - 32) - 1) / (kQBkMax - 32);
   return (unsigned)std::max<int64_t>(stream_grid(nbuckets, kQNB * kQBlock / 16, kQEncPipeGridCap), need);
+}
+
+// The (CodeT, VARIANT) pair of the QSGD kernels: variant 1 and fewer than 128 levels travel as int8,
+// more levels as fp16.  `launch` gets the pair as a QCode tag.
+template <typename CT, int V>
+struct QCode {
+  typedef CT type;
+  static constexpr int variant = V;
+};
+template <typename F>
+static void with_qcode(int32_t variant, int32_t quantum_num, F launch) {
+  if (variant == 1) launch(QCode<int8_t, 1>{});
+  else if (quantum_num < 128) launch(QCode<int8_t, 0>{});
+  else launch(QCode<__half, 0>{});
+}
+
+// 4 codes per load: one 4-B (int8) / 8-B (fp16) load when every rank's slice is aligned
+static int codes_vec(const void* codes, int64_t code_stride, bool half_codes = false) {
+  return (code_stride % 4 == 0) && (half_codes ? al8(codes) : al4(codes));
+}
+
+static inline bool qsgd_fast(int32_t nseg, int64_t nbuckets, int32_t quantum_num, int32_t variant) {
+  return nseg >= 1 && nseg <= kSegLds && nbuckets >= 0 && nbuckets < (int64_t(1) << 24) && quantum_num >= 1 &&
+         (variant == 0 || (variant == 1 && quantum_num < 128));
+}
+// n < 2^31 seen from the unit table: every unit but a segment's last holds kTernUnit elements
+static inline bool tern_fast(int32_t nseg, int64_t nunits) {
+  return nseg >= 1 && nseg <= kSegLds && nunits >= 1 && nunits <= ((int64_t(1) << 31) / kTernUnit) + nseg;
+}
+
+// Bucket-128 encode, nbuckets >= 1: into codes and norms_out (compress), or FUSED with the decode into
+// out (step_w1; no codes, no norms).  The pipelined kernel runs when nothing is injected (no u, no
+// norms_in, no element offset).  The fused step keeps the non-pipelined one: it writes 4 B per element,
+// and the A/B on the ResNet-50 set had the pipelined one slower there (43.1 / 40.6 us at 1024 / 2048
+// workgroups vs 40.3).
+template <bool FUSED, typename XT>
+static grace_status_t qsgd_encode128(const char* name, const XT* x, int64_t xoff, const int64_t* seg_off,
+                                     const int64_t* bkt_off, int32_t nseg, int64_t nbuckets, int32_t quantum_num,
+                                     int32_t variant, const float* u, uint64_t seed, const float* norms_in,
+                                     float* norms_out, void* codes, XT* out, void* stream) {
+  hipStream_t st = as_stream(stream);
+  const bool pipe = !FUSED && !u && !norms_in && xoff == 0;
+  const unsigned grid16 = pipe ? qenc_pipe_grid(nbuckets) : stream_grid(nbuckets, kQNB * kQBlock / 16, kQEncGridCap);
+  with_qcode(variant, quantum_num, [&](auto c) {
+    typedef typename decltype(c)::type CT;
+    constexpr int V = decltype(c)::variant;
+    if constexpr (!FUSED)
+      if (pipe) {
+        qsgd_encode128_pipe_kernel<CT, V, false, XT><<<grid16, kQBlock, 0, st>>>(
+            x, seg_off, bkt_off, nseg, (int32_t)nbuckets, (float)quantum_num, seed, norms_out,
+            reinterpret_cast<CT*>(codes), out);
+        return;
+      }
+    qsgd_encode128_kernel<CT, V, FUSED, XT><<<grid16, kQBlock, 0, st>>>(
+        x, seg_off, bkt_off, nseg, (int32_t)nbuckets, (float)quantum_num, u, seed, norms_in, norms_out,
+        reinterpret_cast<CT*>(codes), out, (uint32_t)xoff);
+  });
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
+
+// Bucket-128 decode + aggregate, 1 <= n < 2^31, nseg <= kSegLds; sr: the ranks' records of a sharded
+// step (their 16-B alignment makes vec 1) instead of rank-major codes and norms
+template <typename OT>
+static grace_status_t qsgd_decode128(const char* name, const void* codes, const float* norms, int64_t code_stride,
+                                     int64_t norm_stride, int32_t world, const int64_t* seg_off,
+                                     const int64_t* bkt_off, int32_t nseg, int64_t n, int32_t quantum_num,
+                                     int32_t variant, int32_t aggregate, float divisor, OT* out, void* stream,
+                                     QShardRec sr = QShardRec{0, 0, 0, 0, nullptr}) {
+  const int vec = codes_vec(codes, code_stride, variant == 0 && quantum_num >= 128);
+  const unsigned bgrid = stream_grid((n + 127) / 128 + nseg, kQNB * kQBlock / 16, kQGridCap);
+  hipStream_t st = as_stream(stream);
+  with_qcode(variant, quantum_num, [&](auto c) {
+    typedef typename decltype(c)::type CT;
+    qsgd_decode_bkt_kernel<CT, decltype(c)::variant, OT><<<bgrid, kQBlock, 0, st>>>(
+        reinterpret_cast<const CT*>(codes), norms, code_stride, norm_stride, world, seg_off, bkt_off, nseg,
+        (float)quantum_num, divisor, aggregate, vec, out, sr);
+  });
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
+
+// tern_encode_kernel on caller-supplied uniforms u, or on the device generator
+template <bool FUSED, typename XT>
+static void tern_encode(int64_t nunits, hipStream_t st, const XT* x, const int64_t* seg_off, const int64_t* unit_off,
+                        int32_t nseg, const TernSlot* w, const float* u, uint64_t seed, int8_t* codes, XT* out,
+                        const float* clip_in, float* scalars, int64_t unit0 = 0, int64_t xoff = 0) {
+  if (u)
+    tern_encode_kernel<FUSED, true, XT><<<(unsigned)nunits, kTernBlock, 0, st>>>(
+        x, seg_off, unit_off, nseg, w, u, seed, codes, out, clip_in, scalars, unit0, xoff);
+  else
+    tern_encode_kernel<FUSED, false, XT><<<(unsigned)nunits, kTernBlock, 0, st>>>(
+        x, seg_off, unit_off, nseg, w, u, seed, codes, out, clip_in, scalars, unit0, xoff);
+}
+
+// the statistics pass, then the encode: into codes (compress), or FUSED with the decode into out (step_w1)
+template <bool FUSED, typename XT>
+static grace_status_t tern_stats_encode(const char* name, const XT* x, const int64_t* seg_off, const int64_t* unit_off,
+                                        int32_t nseg, int64_t nunits, const float* clip_in, const float* u,
+                                        uint64_t seed, int8_t* codes, float* scalars, void* ws, XT* out, void* stream) {
+  TernSlot* const w = reinterpret_cast<TernSlot*>(ws);
+  hipStream_t st = as_stream(stream);
+  tern_stats_kernel<XT><<<(unsigned)nunits, kQBlock, 0, st>>>(x, seg_off, unit_off, nseg, clip_in, w, scalars);
+  GRACE_CHECK_LAUNCH(name);
+  tern_encode<FUSED, XT>(nunits, st, x, seg_off, unit_off, nseg, w, u, seed, codes, out, clip_in, scalars);
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
+
+// the row decode's kernel for a float or a bfloat16 result (two kernels on purpose: see the bf16 one)
+static auto tern_decode_row_for(float*) { return tern_decode_row_kernel; }
+static auto tern_decode_row_for(uint16_t*) { return tern_decode_row_bf16_kernel; }
+
+// row decode + aggregate, 1 <= n < 2^31, nseg <= kSegLds
+template <typename OT>
+static grace_status_t tern_decode_rows(const char* name, const int8_t* codes, const float* scalars,
+                                       int64_t code_stride, int64_t scal_stride, int32_t world, const int64_t* seg_off,
+                                       int32_t nseg, int64_t n, int32_t aggregate, float divisor, OT* out,
+                                       void* stream) {
+  const int vec = codes_vec(codes, code_stride, false);
+  tern_decode_row_for(out)<<<stream_grid((n + 127) / 128, kQNB * kQBlock / 16, kQGridCap), kQBlock, 0,
+                             as_stream(stream)>>>(codes, scalars, code_stride, scal_stride, world, seg_off, nseg,
+                                                  (int32_t)n, divisor, aggregate, vec, out);
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
 }
 
 extern "C" {
@@ -2076,20 +2206,8 @@ grace_status_t grace_qsgd_step_w1(const float* x, const int64_t* seg_off, const 
                     (variant == 0 || (variant == 1 && quantum_num < 128)),
                 "grace_qsgd_step_w1: bad arguments (bucket 128, <= kSegLds segments)");
   if (nbuckets == 0) return GRACE_OK;
-  hipStream_t st = as_stream(stream);
-  // the fused step keeps the non-pipelined kernel: it writes 4 B per element, and the A/B on the
-  // ResNet-50 set had the pipelined one slower there (43.1 / 40.6 us at 1024 / 2048 workgroups vs 40.3)
-  const unsigned grid16 = stream_grid(nbuckets, kQNB * kQBlock / 16, kQEncGridCap);
-#define GRACE_QSTEP128(CT, V)                                                                        \
-  qsgd_encode128_kernel<CT, V, true><<<grid16, kQBlock, 0, st>>>(x, seg_off, bkt_off, nseg, (int32_t)nbuckets, \
-                                                                (float)quantum_num, u, seed, nullptr, nullptr, \
-                                                                nullptr, out)
-  if (variant == 1) GRACE_QSTEP128(int8_t, 1);
-  else if (quantum_num < 128) GRACE_QSTEP128(int8_t, 0);
-  else GRACE_QSTEP128(__half, 0);
-#undef GRACE_QSTEP128
-  GRACE_CHECK_LAUNCH("grace_qsgd_step_w1");
-  return GRACE_OK;
+  return qsgd_encode128<true, float>("grace_qsgd_step_w1", x, 0, seg_off, bkt_off, nseg, nbuckets, quantum_num, variant,
+                                     u, seed, nullptr, nullptr, nullptr, out, stream);
 }
 
 int32_t grace_qsgd_seg_max(void) { return kSegLds; }
@@ -2103,41 +2221,17 @@ grace_status_t grace_qsgd_compress_at(const float* x, int64_t xoff, const int64_
                 "grace_qsgd_compress: bad arguments");
   if (nbuckets == 0) return GRACE_OK;
   GRACE_REQUIRE(variant == 0 || (variant == 1 && quantum_num < 128), "grace_qsgd_compress: bad variant");
+  if (bucket_size == 128 && nseg <= kSegLds && nbuckets < (int64_t(1) << 24))   // n < 2^31
+    return qsgd_encode128<false, float>("grace_qsgd_compress", x, xoff, seg_off, bkt_off, nseg, nbuckets, quantum_num,
+                                        variant, u, seed, norms_in, norms_out, codes, nullptr, stream);
   const unsigned grid = stream_grid(nbuckets, kQNB * kQBlock / 32, kQGridCap);
   hipStream_t st = as_stream(stream);
-  if (bucket_size == 128 && nseg <= kSegLds && nbuckets < (int64_t(1) << 24)) {   // n < 2^31
-    const bool pipe = !u && !norms_in && xoff == 0;
-    const unsigned grid16 = pipe ? qenc_pipe_grid(nbuckets) : stream_grid(nbuckets, kQNB * kQBlock / 16, kQEncGridCap);
-#define GRACE_QENC128(CT, V)                                                                         \
-  do { if (pipe)                                                                                          \
-    qsgd_encode128_pipe_kernel<CT, V, false, float><<<grid16, kQBlock, 0, st>>>(x, seg_off, bkt_off, nseg, (int32_t)nbuckets, \
-                                                               (float)quantum_num, seed, norms_out,  \
-                                                               reinterpret_cast<CT*>(codes), nullptr); \
-  else                                                                                               \
-    qsgd_encode128_kernel<CT, V, false, float><<<grid16, kQBlock, 0, st>>>(x, seg_off, bkt_off, nseg, (int32_t)nbuckets, \
-                                                          (float)quantum_num, u, seed, norms_in,      \
-                                                          norms_out, reinterpret_cast<CT*>(codes),    \
-                                                          nullptr, (uint32_t)xoff); } while (0)
-    if (variant == 1) GRACE_QENC128(int8_t, 1);
-    else if (quantum_num < 128) GRACE_QENC128(int8_t, 0);
-    else GRACE_QENC128(__half, 0);
-#undef GRACE_QENC128
-    GRACE_CHECK_LAUNCH("grace_qsgd_compress");
-    return GRACE_OK;
-  }
-  if (variant == 1) {
-    qsgd_encode_kernel<int8_t, 1><<<grid, kQBlock, 0, st>>>(x, seg_off, bkt_off, nseg, nbuckets, bucket_size,
-                                                           (float)quantum_num, u, seed, norms_in, norms_out,
-                                                           reinterpret_cast<int8_t*>(codes), xoff);
-  } else if (quantum_num < 128) {
-    qsgd_encode_kernel<int8_t, 0><<<grid, kQBlock, 0, st>>>(x, seg_off, bkt_off, nseg, nbuckets, bucket_size,
-                                                           (float)quantum_num, u, seed, norms_in, norms_out,
-                                                           reinterpret_cast<int8_t*>(codes), xoff);
-  } else {
-    qsgd_encode_kernel<__half, 0><<<grid, kQBlock, 0, st>>>(x, seg_off, bkt_off, nseg, nbuckets, bucket_size,
-                                                           (float)quantum_num, u, seed, norms_in, norms_out,
-                                                           reinterpret_cast<__half*>(codes), xoff);
-  }
+  with_qcode(variant, quantum_num, [&](auto c) {
+    typedef typename decltype(c)::type CT;
+    qsgd_encode_kernel<CT, decltype(c)::variant><<<grid, kQBlock, 0, st>>>(
+        x, seg_off, bkt_off, nseg, nbuckets, bucket_size, (float)quantum_num, u, seed, norms_in, norms_out,
+        reinterpret_cast<CT*>(codes), xoff);
+  });
   GRACE_CHECK_LAUNCH("grace_qsgd_compress");
   return GRACE_OK;
 }
@@ -2168,8 +2262,7 @@ grace_status_t grace_qsgd_global_compress(const float* x, int64_t n, int32_t qua
   qsgd_global_norm_kernel<<<1, kQBlock, 0, st>>>(part, nparts, norm_in, norm_out);
   GRACE_CHECK_LAUNCH("grace_qsgd_global_compress");
   const unsigned grid = stream_grid((n + 3) / 4, kQBlock, 4096);
-  const int aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(u)) & 15) == 0 &&
-                      (reinterpret_cast<uintptr_t>(codes) & (quantum_num < 128 ? 3 : 7)) == 0;
+  const int aligned = al16(x) && al16(u) && (quantum_num < 128 ? al4(codes) : al8(codes));
   if (quantum_num < 128)
     qsgd_global_encode_kernel<int8_t><<<grid, kQBlock, 0, st>>>(x, n, norm_out, (float)quantum_num, u, seed,
                                                                 reinterpret_cast<int8_t*>(codes), aligned);
@@ -2188,39 +2281,26 @@ grace_status_t grace_qsgd_decompress(const void* codes, const float* norms, int6
   GRACE_REQUIRE(codes && norms && seg_off && bkt_off && out && world >= 1 && nseg >= 1 && n >= 0,
                 "grace_qsgd_decompress: bad arguments");
   if (n == 0) return GRACE_OK;
+  const bool b128 = bucket_size == 128;
+  if (b128 && nseg <= kSegLds && n < (int64_t(1) << 31))
+    return qsgd_decode128<float>("grace_qsgd_decompress", codes, norms, code_stride, norm_stride, world, seg_off,
+                                 bkt_off, nseg, n, quantum_num, variant, aggregate, divisor, out, stream);
   const unsigned grid = stream_grid((n + kDecRound - 1) / kDecRound, 1, 4096);
   hipStream_t st = as_stream(stream);
-  // 4 codes per load: one 4-B (int8) / 8-B (fp16) load when every rank's slice is aligned
-  const int64_t cbytes = variant == 0 && quantum_num >= 128 ? 2 : 1;
-  const int vec = (code_stride % 4 == 0) && ((uintptr_t)codes % (4 * cbytes) == 0);
-#define GRACE_QDEC(CT, V, B)                                                                         \
-  qsgd_decode_kernel<CT, V, B><<<grid, kQBlock, 0, st>>>(reinterpret_cast<const CT*>(codes), norms,  \
-                                                         code_stride, norm_stride, world, seg_off,   \
-                                                         bkt_off, nseg, n, bucket_size,              \
-                                                         (float)quantum_num, divisor, aggregate, vec, out)
-  const bool b128 = bucket_size == 128;
-  if (b128 && nseg <= kSegLds && n < (int64_t(1) << 31)) {
-    const unsigned bgrid = stream_grid((n + 127) / 128 + nseg, kQNB * kQBlock / 16, kQGridCap);
-#define GRACE_QDECB(CT, V)                                                                          \
-  qsgd_decode_bkt_kernel<CT, V><<<bgrid, kQBlock, 0, st>>>(reinterpret_cast<const CT*>(codes), norms, \
-                                                          code_stride, norm_stride, world, seg_off,  \
-                                                          bkt_off, nseg, (float)quantum_num, divisor, \
-                                                          aggregate, vec, out)
-    if (variant == 1) GRACE_QDECB(int8_t, 1);
-    else if (quantum_num < 128) GRACE_QDECB(int8_t, 0);
-    else GRACE_QDECB(__half, 0);
-#undef GRACE_QDECB
-    GRACE_CHECK_LAUNCH("grace_qsgd_decompress");
-    return GRACE_OK;
-  }
-  if (variant == 1) {
-    if (b128) GRACE_QDEC(int8_t, 1, true); else GRACE_QDEC(int8_t, 1, false);
-  } else if (quantum_num < 128) {
-    if (b128) GRACE_QDEC(int8_t, 0, true); else GRACE_QDEC(int8_t, 0, false);
-  } else {
-    if (b128) GRACE_QDEC(__half, 0, true); else GRACE_QDEC(__half, 0, false);
-  }
-#undef GRACE_QDEC
+  const int vec = codes_vec(codes, code_stride, variant == 0 && quantum_num >= 128);
+  with_qcode(variant, quantum_num, [&](auto c) {
+    typedef typename decltype(c)::type CT;
+    constexpr int V = decltype(c)::variant;
+    const CT* const cd = reinterpret_cast<const CT*>(codes);
+    if (b128)
+      qsgd_decode_kernel<CT, V, true><<<grid, kQBlock, 0, st>>>(cd, norms, code_stride, norm_stride, world, seg_off,
+                                                                bkt_off, nseg, n, bucket_size, (float)quantum_num,
+                                                                divisor, aggregate, vec, out);
+    else
+      qsgd_decode_kernel<CT, V, false><<<grid, kQBlock, 0, st>>>(cd, norms, code_stride, norm_stride, world, seg_off,
+                                                                 bkt_off, nseg, n, bucket_size, (float)quantum_num,
+                                                                 divisor, aggregate, vec, out);
+  });
   GRACE_CHECK_LAUNCH("grace_qsgd_decompress");
   return GRACE_OK;
 }
@@ -2232,25 +2312,15 @@ grace_status_t grace_qsgd_decompress_records(const void* records, int64_t rec_by
   const int64_t cbytes = variant == 0 && quantum_num >= 128 ? 2 : 1;
   GRACE_REQUIRE(records && rank_lo && seg_off && bkt_off && out && world >= 1 && nseg >= 1 && n >= 0 &&
                     units_per_rank >= 1 && nseg <= kSegLds && n < (int64_t(1) << 31) && rec_bytes % 16 == 0 &&
-                    norm_off_bytes % 16 == 0 && norm_off_bytes < rec_bytes && (uintptr_t)records % 16 == 0,
+                    norm_off_bytes % 16 == 0 && norm_off_bytes < rec_bytes && al16(records),
                 "grace_qsgd_decompress_records: bad arguments (16-B aligned records and norms, nseg <= 512)");
   GRACE_REQUIRE(variant == 0 || (variant == 1 && quantum_num < 128), "grace_qsgd_decompress_records: bad variant");
   if (n == 0) return GRACE_OK;
   const char* rec = reinterpret_cast<const char*>(records);
   const QShardRec sr{units_per_rank, rec_bytes / cbytes, rec_bytes / 4, norm_off_bytes / 4, rank_lo};
   const float* norms = reinterpret_cast<const float*>(rec);
-  const unsigned bgrid = stream_grid((n + 127) / 128 + nseg, kQNB * kQBlock / 16, kQGridCap);
-  hipStream_t st = as_stream(stream);
-#define GRACE_QDECR(CT, V)                                                                           \
-  qsgd_decode_bkt_kernel<CT, V><<<bgrid, kQBlock, 0, st>>>(reinterpret_cast<const CT*>(rec), norms, 0, 0, 1, \
-                                                          seg_off, bkt_off, nseg, (float)quantum_num, 1.0f, 0, \
-                                                          1, out, sr)
-  if (variant == 1) GRACE_QDECR(int8_t, 1);
-  else if (quantum_num < 128) GRACE_QDECR(int8_t, 0);
-  else GRACE_QDECR(__half, 0);
-#undef GRACE_QDECR
-  GRACE_CHECK_LAUNCH("grace_qsgd_decompress_records");
-  return GRACE_OK;
+  return qsgd_decode128<float>("grace_qsgd_decompress_records", rec, norms, 0, 0, 1, seg_off, bkt_off, nseg, n,
+                               quantum_num, variant, 0, 1.0f, out, stream, sr);
 }
 
 grace_status_t grace_terngrad_decompress_records(const void* records, int64_t rec_bytes, int32_t world,
@@ -2259,7 +2329,7 @@ grace_status_t grace_terngrad_decompress_records(const void* records, int64_t re
                                                  void* stream) {
   GRACE_REQUIRE(records && rank_lo && scalars && seg_off && out && world >= 1 && world <= kRecRanksMax && nseg >= 1 &&
                     nseg <= kSegLds && n >= 0 && n < (int64_t(1) << 31) && rec_bytes >= 16 && rec_bytes % 16 == 0 &&
-                    (uintptr_t)records % 16 == 0 && (uintptr_t)out % 16 == 0,
+                    al16(records) && al16(out),
                 "grace_terngrad_decompress_records: bad arguments (1 <= world <= 64, nseg <= 512, n < 2^31, "
                 "16-B aligned records of a 16-B multiple, 16-B aligned out)");
   if (n == 0) return GRACE_OK;
@@ -2279,18 +2349,8 @@ grace_status_t grace_terngrad_compress(const float* x, const int64_t* seg_off, c
                                        void* stream) {
   GRACE_REQUIRE(x && seg_off && unit_off && nseg >= 1 && nunits >= 1 && codes && scalars && ws,
                 "grace_terngrad_compress: bad arguments");
-  TernSlot* const w = reinterpret_cast<TernSlot*>(ws);
-  tern_stats_kernel<<<(unsigned)nunits, kQBlock, 0, as_stream(stream)>>>(x, seg_off, unit_off, nseg, clip_in, w,
-                                                                       scalars);
-  GRACE_CHECK_LAUNCH("grace_terngrad_compress");
-  if (u)
-    tern_encode_kernel<false, true, float><<<(unsigned)nunits, kTernBlock, 0, as_stream(stream)>>>(
-        x, seg_off, unit_off, nseg, w, u, seed, codes, nullptr, clip_in, scalars);
-  else
-    tern_encode_kernel<false, false, float><<<(unsigned)nunits, kTernBlock, 0, as_stream(stream)>>>(
-        x, seg_off, unit_off, nseg, w, u, seed, codes, nullptr, clip_in, scalars);
-  GRACE_CHECK_LAUNCH("grace_terngrad_compress");
-  return GRACE_OK;
+  return tern_stats_encode<false, float>("grace_terngrad_compress", x, seg_off, unit_off, nseg, nunits, clip_in, u,
+                                         seed, codes, scalars, ws, nullptr, stream);
 }
 
 int32_t grace_terngrad_slot_bytes(void) { return (int32_t)sizeof(TernSlot); }
@@ -2299,7 +2359,7 @@ grace_status_t grace_terngrad_shard_stats(const float* x, int64_t xoff, const in
                                           const int64_t* unit_off, int32_t nseg, int64_t unit0, int64_t nunits_local,
                                           void* ws, void* stream) {
   GRACE_REQUIRE(x && seg_off && unit_off && nseg >= 1 && unit0 >= 0 && nunits_local >= 0 && xoff >= 0 && ws &&
-                    (reinterpret_cast<uintptr_t>(x) & 15) == 0,
+                    al16(x),
                 "grace_terngrad_shard_stats: bad arguments (16-B aligned shard)");
   if (nunits_local == 0) return GRACE_OK;
   tern_stats_kernel<<<(unsigned)nunits_local, kQBlock, 0, as_stream(stream)>>>(
@@ -2313,17 +2373,12 @@ grace_status_t grace_terngrad_shard_encode(const float* x, int64_t xoff, const i
                                            int64_t nunits_local, const float* clip_in, const float* u, uint64_t seed,
                                            int8_t* codes, const void* ws, void* stream) {
   GRACE_REQUIRE(x && seg_off && unit_off && nseg >= 1 && unit0 >= 0 && nunits_local >= 0 && xoff >= 0 && codes &&
-                    ws && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(u) |
-                            reinterpret_cast<uintptr_t>(codes)) & 15) == 0,
+                    ws && al16(x) && al16(u) && al16(codes),
                 "grace_terngrad_shard_encode: bad arguments (16-B aligned shard, u and codes)");
   if (nunits_local == 0) return GRACE_OK;
-  const TernSlot* w = reinterpret_cast<const TernSlot*>(ws);
-  if (u)
-    tern_encode_kernel<false, true, float><<<(unsigned)nunits_local, kTernBlock, 0, as_stream(stream)>>>(
-        x, seg_off, unit_off, nseg, w, u, seed, codes, nullptr, clip_in, nullptr, unit0, xoff);
-  else
-    tern_encode_kernel<false, false, float><<<(unsigned)nunits_local, kTernBlock, 0, as_stream(stream)>>>(
-        x, seg_off, unit_off, nseg, w, u, seed, codes, nullptr, clip_in, nullptr, unit0, xoff);
+  tern_encode<false, float>(nunits_local, as_stream(stream), x, seg_off, unit_off, nseg,
+                            reinterpret_cast<const TernSlot*>(ws), u, seed, codes, nullptr, clip_in, nullptr, unit0,
+                            xoff);
   GRACE_CHECK_LAUNCH("grace_terngrad_shard_encode");
   return GRACE_OK;
 }
@@ -2340,21 +2395,10 @@ grace_status_t grace_terngrad_scalars(const int64_t* seg_off, const int64_t* uni
 grace_status_t grace_terngrad_step_w1(const float* x, const int64_t* seg_off, const int64_t* unit_off, int32_t nseg,
                                      int64_t nunits, const float* clip_in, const float* u, uint64_t seed,
                                      float* scalars, void* ws, float* out, void* stream) {
-  GRACE_REQUIRE(x && seg_off && unit_off && nseg >= 1 && nunits >= 1 && scalars && ws && out &&
-                    ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+  GRACE_REQUIRE(x && seg_off && unit_off && nseg >= 1 && nunits >= 1 && scalars && ws && out && al16(x) && al16(out),
                 "grace_terngrad_step_w1: bad arguments (16-B aligned x and out)");
-  TernSlot* const w = reinterpret_cast<TernSlot*>(ws);
-  tern_stats_kernel<<<(unsigned)nunits, kQBlock, 0, as_stream(stream)>>>(x, seg_off, unit_off, nseg, clip_in, w,
-                                                                       scalars);
-  GRACE_CHECK_LAUNCH("grace_terngrad_step_w1");
-  if (u)
-    tern_encode_kernel<true, true><<<(unsigned)nunits, kTernBlock, 0, as_stream(stream)>>>(
-        x, seg_off, unit_off, nseg, w, u, seed, nullptr, out, clip_in, scalars);
-  else
-    tern_encode_kernel<true, false><<<(unsigned)nunits, kTernBlock, 0, as_stream(stream)>>>(
-        x, seg_off, unit_off, nseg, w, u, seed, nullptr, out, clip_in, scalars);
-  GRACE_CHECK_LAUNCH("grace_terngrad_step_w1");
-  return GRACE_OK;
+  return tern_stats_encode<true, float>("grace_terngrad_step_w1", x, seg_off, unit_off, nseg, nunits, clip_in, u, seed,
+                                        nullptr, scalars, ws, out, stream);
 }
 
 grace_status_t grace_terngrad_decompress(const int8_t* codes, const float* scalars, int64_t code_stride,
@@ -2364,14 +2408,10 @@ grace_status_t grace_terngrad_decompress(const int8_t* codes, const float* scala
   GRACE_REQUIRE(codes && scalars && seg_off && out && world >= 1 && nseg >= 1 && n >= 0,
                 "grace_terngrad_decompress: bad arguments");
   if (n == 0) return GRACE_OK;
-  const int vec = (code_stride % 4 == 0) && ((uintptr_t)codes % 4 == 0);
-  if (nseg <= kSegLds && n < (int64_t(1) << 31)) {
-    tern_decode_row_kernel<<<stream_grid((n + 127) / 128, kQNB * kQBlock / 16, kQGridCap), kQBlock, 0,
-                             as_stream(stream)>>>(codes, scalars, code_stride, scal_stride, world, seg_off, nseg,
-                                                  (int32_t)n, divisor, aggregate, vec, out);
-    GRACE_CHECK_LAUNCH("grace_terngrad_decompress");
-    return GRACE_OK;
-  }
+  if (nseg <= kSegLds && n < (int64_t(1) << 31))
+    return tern_decode_rows<float>("grace_terngrad_decompress", codes, scalars, code_stride, scal_stride, world,
+                                   seg_off, nseg, n, aggregate, divisor, out, stream);
+  const int vec = codes_vec(codes, code_stride, false);
   tern_decode_kernel<<<stream_grid((n + kDecRound - 1) / kDecRound, 1, 4096), kQBlock, 0, as_stream(stream)>>>(
       codes, scalars, code_stride, scal_stride, world, seg_off, nseg, n, divisor, aggregate, vec, out);
   GRACE_CHECK_LAUNCH("grace_terngrad_decompress");
@@ -2382,8 +2422,7 @@ grace_status_t grace_natural_compress_at(const float* x, int64_t xoff, int64_t n
                                          uint64_t seed, uint8_t* codes, void* stream) {
   GRACE_REQUIRE(x && codes && n >= 0 && xoff >= 0 && (xoff & 3) == 0, "grace_natural_compress: bad arguments");
   if (n == 0) return GRACE_OK;
-  const int al = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(rand_int)) & 15) == 0 &&
-                 (reinterpret_cast<uintptr_t>(codes) & 3) == 0;
+  const int al = al16(x) && al16(rand_int) && al4(codes);
   natural_encode_kernel<<<stream_grid((n + 3) / 4, kQBlock, 4096), kQBlock, 0, as_stream(stream)>>>(
       x, n, rand_int, seed, codes, al, xoff);
   GRACE_CHECK_LAUNCH("grace_natural_compress");
@@ -2399,8 +2438,7 @@ grace_status_t grace_cnat_compress_at(const float* x, int64_t xoff, int64_t n, c
                                       int32_t deterministic, uint64_t seed, uint8_t* codes, void* stream) {
   GRACE_REQUIRE(x && codes && n >= 0 && xoff >= 0 && (xoff & 3) == 0, "grace_cnat_compress: bad arguments");
   if (n == 0) return GRACE_OK;
-  const int al = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(rand)) & 15) == 0 &&
-                 (reinterpret_cast<uintptr_t>(codes) & 3) == 0;
+  const int al = al16(x) && al16(rand) && al4(codes);
   cnat_encode_kernel<<<stream_grid((n + 3) / 4, kQBlock, 4096), kQBlock, 0, as_stream(stream)>>>(
       x, n, rand, deterministic, seed, codes, al, xoff);
   GRACE_CHECK_LAUNCH("grace_cnat_compress");
@@ -2419,8 +2457,7 @@ grace_status_t grace_natural_decompress(const uint8_t* codes, int64_t stride, in
                 "grace_natural_decompress: bad arguments");
   if (n == 0) return GRACE_OK;
   const unsigned grid = stream_grid((n + 3) / 4, kQBlock, 4096);
-  const int al = (reinterpret_cast<uintptr_t>(codes) & 3) == 0 && (stride % 4 == 0 || world == 1) &&
-                 (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  const int al = al4(codes) && (stride % 4 == 0 || world == 1) && al16(out);
   if (flavour == 0)
     natural_decode_kernel<0><<<grid, kQBlock, 0, as_stream(stream)>>>(codes, stride, world, n, divisor,
                                                                       aggregate, out, al);
@@ -2434,7 +2471,7 @@ grace_status_t grace_natural_decompress(const uint8_t* codes, int64_t stride, in
 grace_status_t grace_fp16_compress(const float* x, void* half_out, int64_t n, void* stream) {
   GRACE_REQUIRE(x && half_out && n >= 0, "grace_fp16_compress: bad arguments");
   if (n == 0) return GRACE_OK;
-  const int al = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(half_out) & 7) == 0;
+  const int al = al16(x) && al8(half_out);
   f32_to_f16_kernel<<<stream_grid((n + 3) / 4, kQBlock, 4096), kQBlock, 0, as_stream(stream)>>>(
       x, reinterpret_cast<__half*>(half_out), n, al);
   GRACE_CHECK_LAUNCH("grace_fp16_compress");
@@ -2444,7 +2481,7 @@ grace_status_t grace_fp16_compress(const float* x, void* half_out, int64_t n, vo
 grace_status_t grace_fp16_decompress(const void* half_in, float* out, int64_t n, void* stream) {
   GRACE_REQUIRE(half_in && out && n >= 0, "grace_fp16_decompress: bad arguments");
   if (n == 0) return GRACE_OK;
-  const int al = (reinterpret_cast<uintptr_t>(half_in) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  const int al = al8(half_in) && al16(out);
   f16_to_f32_kernel<<<stream_grid((n + 3) / 4, kQBlock, 4096), kQBlock, 0, as_stream(stream)>>>(
       reinterpret_cast<const __half*>(half_in), out, n, al, 0, 1, 0, 1.0f);
   GRACE_CHECK_LAUNCH("grace_fp16_decompress");
@@ -2453,8 +2490,7 @@ grace_status_t grace_fp16_decompress(const void* half_in, float* out, int64_t n,
 
 grace_status_t grace_cast_step_w1(const float* x, int64_t n, int32_t mode, uint64_t seed, float* out,
                                   void* stream) {
-  GRACE_REQUIRE(x && out && n >= 0 && mode >= 0 && mode <= 3 &&
-                ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+  GRACE_REQUIRE(x && out && n >= 0 && mode >= 0 && mode <= 3 && al16(x) && al16(out),
                 "grace_cast_step_w1: bad arguments (16-B aligned x and out)");
   if (n == 0) return GRACE_OK;
   const unsigned grid = (unsigned)(((n >> 2) + kQBlock - 1) / kQBlock > 0 ? ((n >> 2) + kQBlock - 1) / kQBlock : 1);
@@ -2474,8 +2510,7 @@ grace_status_t grace_fp16_decompress_aggregate(const void* half_in, int64_t stri
   GRACE_REQUIRE(half_in && out && n >= 0 && world >= 1 && stride >= n && divisor != 0.0f,
                 "grace_fp16_decompress_aggregate: bad arguments");
   if (n == 0) return GRACE_OK;
-  const int al = (reinterpret_cast<uintptr_t>(half_in) & 7) == 0 && (stride & 3) == 0 &&
-                 (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  const int al = al8(half_in) && (stride & 3) == 0 && al16(out);
   f16_to_f32_kernel<<<stream_grid((n + 3) / 4, kQBlock, 4096), kQBlock, 0, as_stream(stream)>>>(
       reinterpret_cast<const __half*>(half_in), out, n, al, stride, world, 1, divisor);
   GRACE_CHECK_LAUNCH("grace_fp16_decompress_aggregate");
@@ -2485,18 +2520,9 @@ grace_status_t grace_fp16_decompress_aggregate(const void* half_in, int64_t stri
 // ------------------------------------------------------------------------------------------------
 // bfloat16 twins (include/grace_hip_quant.h): the same kernels instantiated on
 // 16-bit elements, the fast paths only.  Codes, norms and scalars are the f32 entry points' for the
-// widened gradient; a dense result is the f32 result rounded once.
-static inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline bool qsgd_fast(int32_t nseg, int64_t nbuckets, int32_t quantum_num, int32_t variant) {
-  return nseg >= 1 && nseg <= kSegLds && nbuckets >= 0 && nbuckets < (int64_t(1) << 24) && quantum_num >= 1 &&
-         (variant == 0 || (variant == 1 && quantum_num < 128));
-}
-// n < 2^31 seen from the unit table: every unit but a segment's last holds kTernUnit elements
-static inline bool tern_fast(int32_t nseg, int64_t nunits) {
-  return nseg >= 1 && nseg <= kSegLds && nunits >= 1 && nunits <= ((int64_t(1) << 31) / kTernUnit) + nseg;
-}
-
+// widened gradient; a dense result is the f32 result rounded once.  They stay at the end, in this
+// order: kernels are emitted in the order in which entry points first name an instantiation (DESIGN.md
+// section 1, host-side convention).
 grace_status_t grace_qsgd_compress_at_bf16(const uint16_t* x, int64_t xoff, const int64_t* seg_off,
                                            const int64_t* bkt_off, int32_t nseg, int64_t nbuckets,
                                            int32_t quantum_num, int32_t bucket_size, int32_t variant, const float* u,
@@ -2507,24 +2533,8 @@ grace_status_t grace_qsgd_compress_at_bf16(const uint16_t* x, int64_t xoff, cons
                 "grace_qsgd_compress_at_bf16: bad arguments (bucket 128, <= 512 segments, < 2^24 buckets, "
                 "8-B aligned x)");
   if (nbuckets == 0) return GRACE_OK;
-  hipStream_t st = as_stream(stream);
-  const bool pipe = !u && !norms_in && xoff == 0;
-  const unsigned grid16 = pipe ? qenc_pipe_grid(nbuckets) : stream_grid(nbuckets, kQNB * kQBlock / 16, kQEncGridCap);
-#define GRACE_QENC128B(CT, V)                                                                        \
-  do { if (pipe)                                                                                     \
-    qsgd_encode128_pipe_kernel<CT, V, false, uint16_t><<<grid16, kQBlock, 0, st>>>(                   \
-        x, seg_off, bkt_off, nseg, (int32_t)nbuckets, (float)quantum_num, seed, norms_out,           \
-        reinterpret_cast<CT*>(codes), (uint16_t*)nullptr);                                           \
-  else                                                                                               \
-    qsgd_encode128_kernel<CT, V, false, uint16_t><<<grid16, kQBlock, 0, st>>>(                        \
-        x, seg_off, bkt_off, nseg, (int32_t)nbuckets, (float)quantum_num, u, seed, norms_in, norms_out, \
-        reinterpret_cast<CT*>(codes), (uint16_t*)nullptr, (uint32_t)xoff); } while (0)
-  if (variant == 1) GRACE_QENC128B(int8_t, 1);
-  else if (quantum_num < 128) GRACE_QENC128B(int8_t, 0);
-  else GRACE_QENC128B(__half, 0);
-#undef GRACE_QENC128B
-  GRACE_CHECK_LAUNCH("grace_qsgd_compress_at_bf16");
-  return GRACE_OK;
+  return qsgd_encode128<false, uint16_t>("grace_qsgd_compress_at_bf16", x, xoff, seg_off, bkt_off, nseg, nbuckets,
+                                         quantum_num, variant, u, seed, norms_in, norms_out, codes, nullptr, stream);
 }
 
 grace_status_t grace_qsgd_step_w1_bf16(const uint16_t* x, const int64_t* seg_off, const int64_t* bkt_off,
@@ -2535,18 +2545,8 @@ grace_status_t grace_qsgd_step_w1_bf16(const uint16_t* x, const int64_t* seg_off
                 "grace_qsgd_step_w1_bf16: bad arguments (bucket 128, <= 512 segments, < 2^24 buckets, 8-B aligned "
                 "x and out)");
   if (nbuckets == 0) return GRACE_OK;
-  hipStream_t st = as_stream(stream);
-  const unsigned grid16 = stream_grid(nbuckets, kQNB * kQBlock / 16, kQEncGridCap);
-#define GRACE_QSTEP128B(CT, V)                                                                       \
-  qsgd_encode128_kernel<CT, V, true, uint16_t><<<grid16, kQBlock, 0, st>>>(                           \
-      x, seg_off, bkt_off, nseg, (int32_t)nbuckets, (float)quantum_num, u, seed, nullptr, nullptr,   \
-      (CT*)nullptr, out)
-  if (variant == 1) GRACE_QSTEP128B(int8_t, 1);
-  else if (quantum_num < 128) GRACE_QSTEP128B(int8_t, 0);
-  else GRACE_QSTEP128B(__half, 0);
-#undef GRACE_QSTEP128B
-  GRACE_CHECK_LAUNCH("grace_qsgd_step_w1_bf16");
-  return GRACE_OK;
+  return qsgd_encode128<true, uint16_t>("grace_qsgd_step_w1_bf16", x, 0, seg_off, bkt_off, nseg, nbuckets, quantum_num,
+                                        variant, u, seed, nullptr, nullptr, nullptr, out, stream);
 }
 
 grace_status_t grace_qsgd_decompress_bf16(const void* codes, const float* norms, int64_t code_stride,
@@ -2559,20 +2559,8 @@ grace_status_t grace_qsgd_decompress_bf16(const void* codes, const float* norms,
                     (variant == 0 || (variant == 1 && quantum_num < 128)) && al8(out),
                 "grace_qsgd_decompress_bf16: bad arguments (bucket 128, <= 512 segments, n < 2^31, 8-B aligned out)");
   if (n == 0) return GRACE_OK;
-  const int64_t cbytes = variant == 0 && quantum_num >= 128 ? 2 : 1;
-  const int vec = (code_stride % 4 == 0) && ((uintptr_t)codes % (4 * cbytes) == 0);
-  const unsigned bgrid = stream_grid((n + 127) / 128 + nseg, kQNB * kQBlock / 16, kQGridCap);
-  hipStream_t st = as_stream(stream);
-#define GRACE_QDECBB(CT, V)                                                                          \
-  qsgd_decode_bkt_kernel<CT, V, uint16_t><<<bgrid, kQBlock, 0, st>>>(                                 \
-      reinterpret_cast<const CT*>(codes), norms, code_stride, norm_stride, world, seg_off, bkt_off, nseg, \
-      (float)quantum_num, divisor, aggregate, vec, out)
-  if (variant == 1) GRACE_QDECBB(int8_t, 1);
-  else if (quantum_num < 128) GRACE_QDECBB(int8_t, 0);
-  else GRACE_QDECBB(__half, 0);
-#undef GRACE_QDECBB
-  GRACE_CHECK_LAUNCH("grace_qsgd_decompress_bf16");
-  return GRACE_OK;
+  return qsgd_decode128<uint16_t>("grace_qsgd_decompress_bf16", codes, norms, code_stride, norm_stride, world, seg_off,
+                                  bkt_off, nseg, n, quantum_num, variant, aggregate, divisor, out, stream);
 }
 
 grace_status_t grace_terngrad_compress_bf16(const uint16_t* x, const int64_t* seg_off, const int64_t* unit_off,
@@ -2581,18 +2569,8 @@ grace_status_t grace_terngrad_compress_bf16(const uint16_t* x, const int64_t* se
   GRACE_REQUIRE(x && seg_off && unit_off && codes && scalars && ws && tern_fast(nseg, nunits) && al8(x) && al16(u),
                 "grace_terngrad_compress_bf16: bad arguments (<= 512 segments, n < 2^31, 8-B aligned x, 16-B "
                 "aligned u)");
-  TernSlot* const w = reinterpret_cast<TernSlot*>(ws);
-  hipStream_t st = as_stream(stream);
-  tern_stats_kernel<uint16_t><<<(unsigned)nunits, kQBlock, 0, st>>>(x, seg_off, unit_off, nseg, clip_in, w, scalars);
-  GRACE_CHECK_LAUNCH("grace_terngrad_compress_bf16");
-  if (u)
-    tern_encode_kernel<false, true, uint16_t><<<(unsigned)nunits, kTernBlock, 0, st>>>(
-        x, seg_off, unit_off, nseg, w, u, seed, codes, (uint16_t*)nullptr, clip_in, scalars);
-  else
-    tern_encode_kernel<false, false, uint16_t><<<(unsigned)nunits, kTernBlock, 0, st>>>(
-        x, seg_off, unit_off, nseg, w, u, seed, codes, (uint16_t*)nullptr, clip_in, scalars);
-  GRACE_CHECK_LAUNCH("grace_terngrad_compress_bf16");
-  return GRACE_OK;
+  return tern_stats_encode<false, uint16_t>("grace_terngrad_compress_bf16", x, seg_off, unit_off, nseg, nunits,
+                                            clip_in, u, seed, codes, scalars, ws, nullptr, stream);
 }
 
 grace_status_t grace_terngrad_step_w1_bf16(const uint16_t* x, const int64_t* seg_off, const int64_t* unit_off,
@@ -2602,18 +2580,8 @@ grace_status_t grace_terngrad_step_w1_bf16(const uint16_t* x, const int64_t* seg
                     al16(u),
                 "grace_terngrad_step_w1_bf16: bad arguments (<= 512 segments, n < 2^31, 8-B aligned x and out, "
                 "16-B aligned u)");
-  TernSlot* const w = reinterpret_cast<TernSlot*>(ws);
-  hipStream_t st = as_stream(stream);
-  tern_stats_kernel<uint16_t><<<(unsigned)nunits, kQBlock, 0, st>>>(x, seg_off, unit_off, nseg, clip_in, w, scalars);
-  GRACE_CHECK_LAUNCH("grace_terngrad_step_w1_bf16");
-  if (u)
-    tern_encode_kernel<true, true, uint16_t><<<(unsigned)nunits, kTernBlock, 0, st>>>(
-        x, seg_off, unit_off, nseg, w, u, seed, nullptr, out, clip_in, scalars);
-  else
-    tern_encode_kernel<true, false, uint16_t><<<(unsigned)nunits, kTernBlock, 0, st>>>(
-        x, seg_off, unit_off, nseg, w, u, seed, nullptr, out, clip_in, scalars);
-  GRACE_CHECK_LAUNCH("grace_terngrad_step_w1_bf16");
-  return GRACE_OK;
+  return tern_stats_encode<true, uint16_t>("grace_terngrad_step_w1_bf16", x, seg_off, unit_off, nseg, nunits, clip_in,
+                                           u, seed, nullptr, scalars, ws, out, stream);
 }
 
 grace_status_t grace_terngrad_decompress_bf16(const int8_t* codes, const float* scalars, int64_t code_stride,
@@ -2624,12 +2592,8 @@ grace_status_t grace_terngrad_decompress_bf16(const int8_t* codes, const float* 
                     n < (int64_t(1) << 31) && al8(out),
                 "grace_terngrad_decompress_bf16: bad arguments (<= 512 segments, n < 2^31, 8-B aligned out)");
   if (n == 0) return GRACE_OK;
-  const int vec = (code_stride % 4 == 0) && ((uintptr_t)codes % 4 == 0);
-  tern_decode_row_bf16_kernel<<<stream_grid((n + 127) / 128, kQNB * kQBlock / 16, kQGridCap), kQBlock, 0,
-                                as_stream(stream)>>>(codes, scalars, code_stride, scal_stride, world, seg_off, nseg,
-                                                     (int32_t)n, divisor, aggregate, vec, out);
-  GRACE_CHECK_LAUNCH("grace_terngrad_decompress_bf16");
-  return GRACE_OK;
+  return tern_decode_rows<uint16_t>("grace_terngrad_decompress_bf16", codes, scalars, code_stride, scal_stride, world,
+                                    seg_off, nseg, n, aggregate, divisor, out, stream);
 }
 
 }  // extern "C"

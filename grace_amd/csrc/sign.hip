@@ -23,11 +23,6 @@ constexpr int kSBlock = 256;
 constexpr int kU = 4;             // quads per lane per trip, all loaded before the first is used
 constexpr int kEfParts = 2048;    // stream_grid's cap: the most f64 partials pass A can write
 
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-static inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-static inline bool al2(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1u) == 0; }
-
 // ------------------------------------------------------------------------------------------------
 // Element access: a quad is one 16-B (f32) or one 8-B (bf16) load or store.
 template <typename E>

@@ -871,30 +871,94 @@ __global__ __launch_bounds__(kSBlock) void rec_sub_kernel(const uint32_t* __rest
     r[idx[j]] = r[idx[j]] - vals[j];
 }
 
+// The threshold workspace (grace_threshold_workspace_bytes), as every entry point sees it
+struct ThrWs {
+  int64_t nch;        // chunks of kThrChunk elements
+  uint32_t* meta;     // bound bits, count, recount flag (the caller reads the first 16 bytes)
+  ThrPart* part;      // [nch] per-chunk statistics
+  uint32_t* offs;     // [nch] exclusive offsets
+};
+
+static ThrWs thr_carve(const void* ws, int64_t n) {
+  const int64_t nch = (n + kThrChunk - 1) / kThrChunk;
+  char* p = reinterpret_cast<char*>(const_cast<void*>(ws));
+  return ThrWs{nch, reinterpret_cast<uint32_t*>(p), reinterpret_cast<ThrPart*>(p + 64),
+               reinterpret_cast<uint32_t*>(p + 64 + sizeof(ThrPart) * nch)};
+}
+
 // grace_threshold_step_w1 and its bf16 twin: the speculative pass, then the gated fix-up
 template <typename GT>
 static grace_status_t threshold_step_w1(const char* name, const GT* g, float* residual, int32_t mode, float beta,
                                         float gamma, int64_t n, float thr, void* ws, GT* out, hipStream_t s) {
-  const int64_t nch = (n + kThrChunk - 1) / kThrChunk;
-  char* p = reinterpret_cast<char*>(ws);
-  uint32_t* meta = reinterpret_cast<uint32_t*>(p);
-  ThrPart* part = reinterpret_cast<ThrPart*>(p + 64);
+  const ThrWs w = thr_carve(ws, n);
   const unsigned fgrid = stream_grid(n, kSBlock, 1024);
   if (mode == 0) {
-    thr_spec_kernel<0, GT><<<(unsigned)nch, kSBlock, 0, s>>>(g, nullptr, beta, gamma, n, thr, out, part, meta);
+    thr_spec_kernel<0, GT><<<(unsigned)w.nch, kSBlock, 0, s>>>(g, nullptr, beta, gamma, n, thr, out, w.part, w.meta);
     GRACE_CHECK_LAUNCH(name);
-    thr_fix_kernel<0, GT><<<fgrid, kSBlock, 0, s>>>(g, nullptr, n, thr, meta, out);
+    thr_fix_kernel<0, GT><<<fgrid, kSBlock, 0, s>>>(g, nullptr, n, thr, w.meta, out);
   } else if (mode == 1) {
-    thr_spec_kernel<1, GT><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, thr, out, part, meta);
+    thr_spec_kernel<1, GT><<<(unsigned)w.nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, thr, out, w.part, w.meta);
     GRACE_CHECK_LAUNCH(name);
-    thr_fix_kernel<1, GT><<<fgrid, kSBlock, 0, s>>>(g, residual, n, thr, meta, out);
+    thr_fix_kernel<1, GT><<<fgrid, kSBlock, 0, s>>>(g, residual, n, thr, w.meta, out);
   } else {
-    thr_spec_kernel<2, GT><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, thr, out, part, meta);
+    thr_spec_kernel<2, GT><<<(unsigned)w.nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, thr, out, w.part, w.meta);
     GRACE_CHECK_LAUNCH(name);
-    thr_fix_kernel<2, GT><<<fgrid, kSBlock, 0, s>>>(g, residual, n, thr, meta, out);
+    thr_fix_kernel<2, GT><<<fgrid, kSBlock, 0, s>>>(g, residual, n, thr, w.meta, out);
   }
   GRACE_CHECK_LAUNCH(name);
   return GRACE_OK;
+}
+
+// Stage 1: per-chunk statistics at `bound`, then the one workgroup that derives the final bound and the
+// chunk offsets.  count: (thr, 0, 0); recount: (max(x), 1, 0); count_fixed: (the caller's bound, 1, 1).
+static grace_status_t threshold_count(const char* name, const float* x, int64_t n, float bound, void* ws,
+                                      int final_pass, int fixed_bound, void* stream) {
+  const ThrWs w = thr_carve(ws, n);
+  hipStream_t s = as_stream(stream);
+  thr_stats_kernel<<<(unsigned)w.nch, kSBlock, 0, s>>>(x, n, bound, w.part);
+  GRACE_CHECK_LAUNCH(name);
+  thr_bound_kernel<<<1, 1024, 0, s>>>(w.part, w.nch, bound, w.offs, w.meta, final_pass, fixed_bound);
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
+
+// Stage 3: the ordered compaction, at most `cap` entries; hdr, when given, receives {count, cap}
+template <typename IdxT>
+static grace_status_t threshold_write(const char* name, const float* x, int64_t n, const void* ws, float* vals,
+                                      IdxT* idx, int64_t cap, uint32_t* hdr, void* stream) {
+  const ThrWs w = thr_carve(ws, n);
+  thr_write_kernel<IdxT><<<(unsigned)w.nch, kSBlock, 0, as_stream(stream)>>>(x, n, w.offs, w.meta, vals, idx, cap, hdr);
+  GRACE_CHECK_LAUNCH(name);
+  return GRACE_OK;
+}
+
+// t = beta r + gamma g into r and out (r = g without a residual): the dense pass both sparse random-k steps open with
+static void randomk_pass(const float* g, float* residual, int32_t has_residual, float beta, float gamma, int64_t n,
+                         float* out, hipStream_t s) {
+  const unsigned grid = stream_grid((n + 3) / 4, kSBlock * kRQ, 4096);
+  if (has_residual) randomk_pass_kernel<true><<<grid, kSBlock, 0, s>>>(g, residual, beta, gamma, n, out);
+  else randomk_pass_kernel<false><<<grid, kSBlock, 0, s>>>(g, residual, beta, gamma, n, out);
+}
+
+// A grouping of the dense random-k steps (grace_randomk_group_bytes): the chunks' ends, then every
+// index's 16-bit offset inside its chunk
+struct RkGroup {
+  uint32_t* ends;
+  uint16_t* offs;
+};
+
+static RkGroup rk_carve(const void* buf, int64_t nch) {
+  char* q = reinterpret_cast<char*>(const_cast<void*>(buf));
+  return RkGroup{reinterpret_cast<uint32_t*>(q),
+                 reinterpret_cast<uint16_t*>(q ? q + al256(sizeof(uint32_t) * (size_t)nch) : nullptr)};
+}
+
+// This step's grouping of idx by chunk: into the caller's per-name buffer `grp` (the next step's
+// prev_grp) or, without one, into the workspace behind the grouping's tickets and counts (left zeroed)
+static hipError_t randomk_group(const int64_t* idx, int64_t k, int64_t nch, void* grp, void* ws, hipStream_t s,
+                                RkGroup* g) {
+  *g = rk_carve(grp ? grp : reinterpret_cast<char*>(ws) + group_scratch_bytes(nch), nch);
+  return group_by_chunk<int64_t>(nullptr, idx, k, nch, nullptr, g->offs, g->ends, reinterpret_cast<uint32_t*>(ws), s);
 }
 
 }  // namespace grace
@@ -916,9 +980,7 @@ grace_status_t grace_randomk_step_w1(const float* g, float* residual, int32_t ha
                                      void* stream) {
   GRACE_REQUIRE(g && residual && idx && vals && out && n >= 1 && k >= 0, "grace_randomk_step_w1: bad arguments");
   hipStream_t s = as_stream(stream);
-  const unsigned grid = stream_grid((n + 3) / 4, kSBlock * kRQ, 4096);
-  if (has_residual) randomk_pass_kernel<true><<<grid, kSBlock, 0, s>>>(g, residual, beta, gamma, n, out);
-  else randomk_pass_kernel<false><<<grid, kSBlock, 0, s>>>(g, residual, beta, gamma, n, out);
+  randomk_pass(g, residual, has_residual, beta, gamma, n, out, s);
   GRACE_CHECK_LAUNCH("grace_randomk_step_w1");
   if (k == 0) return GRACE_OK;
   gather_kernel<<<stream_grid(k, kSBlock, 2048), kSBlock, 0, s>>>(residual, idx, k, vals);
@@ -934,9 +996,7 @@ grace_status_t grace_randomk_shard_step(const float* g, float* residual, int32_t
   GRACE_REQUIRE(g && residual && vals && lo >= 0 && m >= 1 && k >= 0 && (k == 0 || idx),
                 "grace_randomk_shard_step: bad arguments");
   hipStream_t s = as_stream(stream);
-  const unsigned grid = stream_grid((m + 3) / 4, kSBlock * kRQ, 4096);
-  if (has_residual) randomk_pass_kernel<true><<<grid, kSBlock, 0, s>>>(g, residual, beta, gamma, m, out);
-  else randomk_pass_kernel<false><<<grid, kSBlock, 0, s>>>(g, residual, beta, gamma, m, out);
+  randomk_pass(g, residual, has_residual, beta, gamma, m, out, s);
   GRACE_CHECK_LAUNCH("grace_randomk_shard_step");
   if (k == 0) return GRACE_OK;
   randomk_shard_gather_kernel<<<stream_grid(k, kSBlock, 2048), kSBlock, 0, s>>>(residual, idx, k, lo, m, vals);
@@ -957,15 +1017,13 @@ grace_status_t grace_randomk_decode(const float* vals, const int64_t* idx, int64
   return GRACE_OK;
 }
 
-size_t grace_randomk_step_w1_dense_workspace_bytes(int64_t n, int64_t k) {
-  const int64_t nch = (n + kRkChunk - 1) / kRkChunk;
-  return group_scratch_bytes(nch) + ((sizeof(uint32_t) * (size_t)nch + 255) & ~(size_t)255) +
-         sizeof(uint16_t) * (size_t)(k < 1 ? 1 : k);
-}
-
 size_t grace_randomk_group_bytes(int64_t n, int64_t k) {
   const int64_t nch = (n + kRkChunk - 1) / kRkChunk;
-  return ((sizeof(uint32_t) * (size_t)nch + 255) & ~(size_t)255) + sizeof(uint16_t) * (size_t)(k < 1 ? 1 : k);
+  return al256(sizeof(uint32_t) * (size_t)nch) + sizeof(uint16_t) * (size_t)(k < 1 ? 1 : k);
+}
+
+size_t grace_randomk_step_w1_dense_workspace_bytes(int64_t n, int64_t k) {
+  return group_scratch_bytes((n + kRkChunk - 1) / kRkChunk) + grace_randomk_group_bytes(n, k);
 }
 
 grace_status_t grace_randomk_step_w1_dense(const float* g, float* residual, int32_t has_residual, float beta,
@@ -979,31 +1037,23 @@ grace_status_t grace_randomk_step_w1_dense(const float* g, float* residual, int3
   GRACE_REQUIRE(nch <= 32768, "grace_randomk_step_w1_dense: n <= 2^28");
   GRACE_REQUIRE(!prev_grp || grp, "grace_randomk_step_w1_dense: a recycled output needs this step's grouping buffer");
   hipStream_t s = as_stream(stream);
-  char* p = reinterpret_cast<char*>(ws);
-  uint32_t* scratch = reinterpret_cast<uint32_t*>(p);   // the grouping's tickets and counts (left zeroed)
-  // this step's grouping: into the caller's per-name buffer `grp` (it becomes the next step's
-  // prev_grp), or into the workspace
-  char* q = grp ? reinterpret_cast<char*>(grp) : p + group_scratch_bytes(nch);
-  const size_t eb = (sizeof(uint32_t) * (size_t)nch + 255) & ~(size_t)255;
-  uint32_t* ends = reinterpret_cast<uint32_t*>(q);
-  uint16_t* offs = reinterpret_cast<uint16_t*>(q + eb);
-  const uint32_t* pends = prev_grp ? reinterpret_cast<const uint32_t*>(prev_grp) : nullptr;
-  const uint16_t* poffs = prev_grp ? reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(prev_grp) + eb) : nullptr;
-  const hipError_t e = group_by_chunk<int64_t>(nullptr, idx, k, nch, nullptr, offs, ends, scratch, s);
+  RkGroup now;
+  const RkGroup prev = rk_carve(prev_grp, nch);
+  const hipError_t e = randomk_group(idx, k, nch, grp, ws, s, &now);
   if (e != hipSuccess) { set_error("grace_randomk_step_w1_dense", e); return GRACE_ERR_HIP; }
   if (prev_grp) {
     if (has_residual)
-      randomk_dense_pass_kernel<true, true><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, offs, ends, out,
-                                                                            poffs, pends);
+      randomk_dense_pass_kernel<true, true><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, now.offs,
+                                                                            now.ends, out, prev.offs, prev.ends);
     else
-      randomk_dense_pass_kernel<false, true><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, offs, ends,
-                                                                             out, poffs, pends);
+      randomk_dense_pass_kernel<false, true><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, now.offs,
+                                                                             now.ends, out, prev.offs, prev.ends);
   } else if (has_residual) {
-    randomk_dense_pass_kernel<true, false><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, offs, ends, out,
-                                                                           nullptr, nullptr);
+    randomk_dense_pass_kernel<true, false><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, now.offs,
+                                                                           now.ends, out, nullptr, nullptr);
   } else {
-    randomk_dense_pass_kernel<false, false><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, offs, ends, out,
-                                                                            nullptr, nullptr);
+    randomk_dense_pass_kernel<false, false><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, now.offs,
+                                                                            now.ends, out, nullptr, nullptr);
   }
   GRACE_CHECK_LAUNCH("grace_randomk_step_w1_dense");
   return GRACE_OK;
@@ -1017,17 +1067,15 @@ grace_status_t grace_randomk_step_w1_dense_bf16(const uint16_t* g, float* residu
                 "grace_randomk_step_w1_dense_bf16: bad arguments (1 <= n <= 2^28, workspace)");
   const int64_t nch = (n + kRkChunk - 1) / kRkChunk;
   hipStream_t s = as_stream(stream);
-  char* p = reinterpret_cast<char*>(ws);   // the f32 entry's workspace layout: scratch, then the grouping
-  uint32_t* scratch = reinterpret_cast<uint32_t*>(p);
-  char* q = p + group_scratch_bytes(nch);
-  uint32_t* ends = reinterpret_cast<uint32_t*>(q);
-  uint16_t* offs = reinterpret_cast<uint16_t*>(q + ((sizeof(uint32_t) * (size_t)nch + 255) & ~(size_t)255));
-  const hipError_t e = group_by_chunk<int64_t>(nullptr, idx, k, nch, nullptr, offs, ends, scratch, s);
+  RkGroup now;
+  const hipError_t e = randomk_group(idx, k, nch, nullptr, ws, s, &now);
   if (e != hipSuccess) { set_error("grace_randomk_step_w1_dense_bf16", e); return GRACE_ERR_HIP; }
   if (has_residual)
-    randomk_dense_pass_bf16_kernel<true><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, offs, ends, out);
+    randomk_dense_pass_bf16_kernel<true><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, now.offs,
+                                                                           now.ends, out);
   else
-    randomk_dense_pass_bf16_kernel<false><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, offs, ends, out);
+    randomk_dense_pass_bf16_kernel<false><<<(unsigned)nch, kSBlock, 0, s>>>(g, residual, beta, gamma, n, now.offs,
+                                                                            now.ends, out);
   GRACE_CHECK_LAUNCH("grace_randomk_step_w1_dense_bf16");
   return GRACE_OK;
 }
@@ -1091,17 +1139,7 @@ size_t grace_threshold_workspace_bytes(int64_t n) {
 // the workspace (first 16 bytes) to size the outputs, then calls grace_threshold_write.
 grace_status_t grace_threshold_count(const float* x, int64_t n, float thr, void* ws, void* stream) {
   GRACE_REQUIRE(x && ws && n >= 1, "grace_threshold_count: bad arguments");
-  const int64_t nch = (n + kThrChunk - 1) / kThrChunk;
-  char* p = reinterpret_cast<char*>(ws);
-  uint32_t* meta = reinterpret_cast<uint32_t*>(p);
-  ThrPart* part = reinterpret_cast<ThrPart*>(p + 64);
-  uint32_t* offs = reinterpret_cast<uint32_t*>(p + 64 + sizeof(ThrPart) * nch);
-  hipStream_t s = as_stream(stream);
-  thr_stats_kernel<<<(unsigned)nch, kSBlock, 0, s>>>(x, n, thr, part);
-  GRACE_CHECK_LAUNCH("grace_threshold_count");
-  thr_bound_kernel<<<1, 1024, 0, s>>>(part, nch, thr, offs, meta, 0, 0);
-  GRACE_CHECK_LAUNCH("grace_threshold_count");
-  return GRACE_OK;
+  return threshold_count("grace_threshold_count", x, n, thr, ws, 0, 0, stream);
 }
 
 grace_status_t grace_threshold_step_w1(const float* g, float* residual, int32_t mode, float beta, float gamma,
@@ -1125,17 +1163,7 @@ grace_status_t grace_threshold_step_w1_bf16(const uint16_t* g, float* residual, 
 // Recount at max(x) (only when max(x) < thr, flagged by stage 1).
 grace_status_t grace_threshold_recount(const float* x, int64_t n, float bound, void* ws, void* stream) {
   GRACE_REQUIRE(x && ws && n >= 1, "grace_threshold_recount: bad arguments");
-  const int64_t nch = (n + kThrChunk - 1) / kThrChunk;
-  char* p = reinterpret_cast<char*>(ws);
-  uint32_t* meta = reinterpret_cast<uint32_t*>(p);
-  ThrPart* part = reinterpret_cast<ThrPart*>(p + 64);
-  uint32_t* offs = reinterpret_cast<uint32_t*>(p + 64 + sizeof(ThrPart) * nch);
-  hipStream_t s = as_stream(stream);
-  thr_stats_kernel<<<(unsigned)nch, kSBlock, 0, s>>>(x, n, bound, part);
-  GRACE_CHECK_LAUNCH("grace_threshold_recount");
-  thr_bound_kernel<<<1, 1024, 0, s>>>(part, nch, bound, offs, meta, 1, 0);
-  GRACE_CHECK_LAUNCH("grace_threshold_recount");
-  return GRACE_OK;
+  return threshold_count("grace_threshold_recount", x, n, bound, ws, 1, 0, stream);
 }
 
 // Stage 1 without any host decision: the recount (max(x) < thr) is decided on the device, so the
@@ -1144,15 +1172,11 @@ grace_status_t grace_threshold_count_dev(const float* x, int64_t n, float thr, v
   GRACE_REQUIRE(x && ws && n >= 1, "grace_threshold_count_dev: bad arguments");
   grace_status_t st = grace_threshold_count(x, n, thr, ws, stream);
   if (st != GRACE_OK) return st;
-  const int64_t nch = (n + kThrChunk - 1) / kThrChunk;
-  char* p = reinterpret_cast<char*>(ws);
-  uint32_t* meta = reinterpret_cast<uint32_t*>(p);
-  ThrPart* part = reinterpret_cast<ThrPart*>(p + 64);
-  uint32_t* offs = reinterpret_cast<uint32_t*>(p + 64 + sizeof(ThrPart) * nch);
+  const ThrWs w = thr_carve(ws, n);
   hipStream_t s = as_stream(stream);
-  thr_restats_kernel<<<(unsigned)nch, kSBlock, 0, s>>>(x, n, meta, part);
+  thr_restats_kernel<<<(unsigned)w.nch, kSBlock, 0, s>>>(x, n, w.meta, w.part);
   GRACE_CHECK_LAUNCH("grace_threshold_count_dev");
-  thr_reoffset_kernel<<<1, 1024, 0, s>>>(part, nch, offs, meta);
+  thr_reoffset_kernel<<<1, 1024, 0, s>>>(w.part, w.nch, w.offs, w.meta);
   GRACE_CHECK_LAUNCH("grace_threshold_count_dev");
   return GRACE_OK;
 }
@@ -1168,14 +1192,7 @@ grace_status_t grace_sparse_sub(const float* vals, const int32_t* idx, int64_t c
 grace_status_t grace_threshold_write(const float* x, int64_t n, const void* ws, float* vals, int32_t* idx,
                                      void* stream) {
   GRACE_REQUIRE(x && ws && n >= 1, "grace_threshold_write: bad arguments");
-  const int64_t nch = (n + kThrChunk - 1) / kThrChunk;
-  const char* p = reinterpret_cast<const char*>(ws);
-  const uint32_t* meta = reinterpret_cast<const uint32_t*>(p);
-  const uint32_t* offs = reinterpret_cast<const uint32_t*>(p + 64 + sizeof(ThrPart) * nch);
-  thr_write_kernel<int32_t><<<(unsigned)nch, kSBlock, 0, as_stream(stream)>>>(x, n, offs, meta, vals, idx, n,
-                                                                           nullptr);
-  GRACE_CHECK_LAUNCH("grace_threshold_write");
-  return GRACE_OK;
+  return threshold_write<int32_t>("grace_threshold_write", x, n, ws, vals, idx, n, nullptr, stream);
 }
 
 grace_status_t grace_randomk_perm_indices(uint64_t seed, int64_t numel, int64_t k, int64_t* idx, void* stream) {
@@ -1202,30 +1219,13 @@ grace_status_t grace_widen_i32(const int32_t* src, int64_t n, int64_t* dst, void
 // f32, NaN never selected), or NaN when thr is +inf (nothing selected).
 grace_status_t grace_threshold_count_fixed(const float* x, int64_t n, float bound, void* ws, void* stream) {
   GRACE_REQUIRE(x && ws && n >= 1, "grace_threshold_count_fixed: bad arguments");
-  const int64_t nch = (n + kThrChunk - 1) / kThrChunk;
-  char* p = reinterpret_cast<char*>(ws);
-  uint32_t* meta = reinterpret_cast<uint32_t*>(p);
-  ThrPart* part = reinterpret_cast<ThrPart*>(p + 64);
-  uint32_t* offs = reinterpret_cast<uint32_t*>(p + 64 + sizeof(ThrPart) * nch);
-  hipStream_t s = as_stream(stream);
-  thr_stats_kernel<<<(unsigned)nch, kSBlock, 0, s>>>(x, n, bound, part);
-  GRACE_CHECK_LAUNCH("grace_threshold_count_fixed");
-  thr_bound_kernel<<<1, 1024, 0, s>>>(part, nch, bound, offs, meta, 1, 1);
-  GRACE_CHECK_LAUNCH("grace_threshold_count_fixed");
-  return GRACE_OK;
+  return threshold_count("grace_threshold_count_fixed", x, n, bound, ws, 1, 1, stream);
 }
 
 grace_status_t grace_threshold_write_i64(const float* x, int64_t n, const void* ws, float* vals, int64_t* idx,
                                          void* stream) {
   GRACE_REQUIRE(x && ws && n >= 1, "grace_threshold_write_i64: bad arguments");
-  const int64_t nch = (n + kThrChunk - 1) / kThrChunk;
-  const char* p = reinterpret_cast<const char*>(ws);
-  const uint32_t* meta = reinterpret_cast<const uint32_t*>(p);
-  const uint32_t* offs = reinterpret_cast<const uint32_t*>(p + 64 + sizeof(ThrPart) * nch);
-  thr_write_kernel<int64_t><<<(unsigned)nch, kSBlock, 0, as_stream(stream)>>>(x, n, offs, meta, vals, idx, n,
-                                                                           nullptr);
-  GRACE_CHECK_LAUNCH("grace_threshold_write_i64");
-  return GRACE_OK;
+  return threshold_write<int64_t>("grace_threshold_write_i64", x, n, ws, vals, idx, n, nullptr, stream);
 }
 
 size_t grace_exchange_record_words(int64_t cap) { return (size_t)(kRecHdr + 2 * cap); }
@@ -1235,15 +1235,9 @@ grace_status_t grace_threshold_write_capped(const float* x, int64_t n, const voi
                                             void* stream) {
   GRACE_REQUIRE(x && ws && rec && n >= 1 && cap >= 1 && cap <= n && n < ((int64_t)1 << 31),
                 "grace_threshold_write_capped: bad arguments (1 <= cap <= n)");
-  const int64_t nch = (n + kThrChunk - 1) / kThrChunk;
-  const char* p = reinterpret_cast<const char*>(ws);
-  const uint32_t* meta = reinterpret_cast<const uint32_t*>(p);
-  const uint32_t* offs = reinterpret_cast<const uint32_t*>(p + 64 + sizeof(ThrPart) * nch);
   float* vals = reinterpret_cast<float*>(rec + kRecHdr);
   int32_t* idx = reinterpret_cast<int32_t*>(rec + kRecHdr + cap);
-  thr_write_kernel<int32_t><<<(unsigned)nch, kSBlock, 0, as_stream(stream)>>>(x, n, offs, meta, vals, idx, cap, rec);
-  GRACE_CHECK_LAUNCH("grace_threshold_write_capped");
-  return GRACE_OK;
+  return threshold_write<int32_t>("grace_threshold_write_capped", x, n, ws, vals, idx, cap, rec, stream);
 }
 
 // Rank-ordered decode + aggregate of W gathered records (stride = grace_exchange_record_words(cap)

@@ -182,8 +182,6 @@ static inline int64_t topk_cap(int64_t n, int64_t k) {
   return c < n ? c : n;
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // parallel exact fallback scratch (see parallel_exact): tickets, counters, histograms, slice counts
 constexpr int kFbWordsHost = 64 + 3 * 2048 + 2 * 1024;
 // the host word every top-k launch reports a run-out to, and the bound of the fallback's waits
@@ -201,15 +199,15 @@ static TopkWs carve(void* ws, int64_t n, int64_t k) {
   // right after ctl, at the same address for every (n, k): the workspace is shared by calls of
   // every shape, and the fallback's tickets and histograms must be zero wherever a call finds them
   w.fb = reinterpret_cast<uint32_t*>(p);
-  p += align256(sizeof(uint32_t) * kFbWordsHost);
+  p += al256(sizeof(uint32_t) * kFbWordsHost);
   w.hist = reinterpret_cast<uint32_t*>(p);
-  p += align256(sizeof(uint32_t) * kHistBins);
+  p += al256(sizeof(uint32_t) * kHistBins);
   w.chist = reinterpret_cast<uint32_t*>(p);
-  p += align256(sizeof(uint32_t) * kCoarseBins);
+  p += al256(sizeof(uint32_t) * kCoarseBins);
   w.shist = reinterpret_cast<uint32_t*>(p);
-  p += align256(sizeof(uint32_t) * kBracketBins);
+  p += al256(sizeof(uint32_t) * kBracketBins);
   w.cand = reinterpret_cast<int2*>(p);
-  p += align256(sizeof(int2) * w.cap);
+  p += al256(sizeof(int2) * w.cap);
   w.bnd = reinterpret_cast<int2*>(p);
   w.hstatus = g_topk_hstatus;
   w.spin_max = g_fb_spin_max;
@@ -218,10 +216,10 @@ static TopkWs carve(void* ws, int64_t n, int64_t k) {
 
 static size_t ws_bytes(int64_t n, int64_t k) {
   const int64_t cap = topk_cap(n, k);
-  return 256 + align256(sizeof(uint32_t) * kHistBins) +
-         align256(sizeof(uint32_t) * kCoarseBins) +
-         align256(sizeof(uint32_t) * kBracketBins) +
-         2 * align256(sizeof(int2) * cap) + align256(sizeof(uint32_t) * kFbWordsHost);
+  return 256 + al256(sizeof(uint32_t) * kHistBins) +
+         al256(sizeof(uint32_t) * kCoarseBins) +
+         al256(sizeof(uint32_t) * kBracketBins) +
+         2 * al256(sizeof(int2) * cap) + al256(sizeof(uint32_t) * kFbWordsHost);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2865,7 +2863,7 @@ int64_t grace_topk_segmented_workspace_bytes(const int64_t* sizes, const int64_t
   if (!sizes || !ks || count < 0) return -1;
   int64_t total = 0;
   for (int32_t i = 0; i < count; ++i)
-    total += (int64_t)align256((size_t)seg_ws_bytes_one(sizes[i] < 1 ? 1 : sizes[i], ks[i] < 1 ? 1 : ks[i]));
+    total += (int64_t)al256((size_t)seg_ws_bytes_one(sizes[i] < 1 ? 1 : sizes[i], ks[i] < 1 ? 1 : ks[i]));
   return total;
 }
 

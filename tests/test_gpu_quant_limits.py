@@ -195,6 +195,37 @@ def test_segments_qsgd_other_buckets(bucket, q):
     check_qsgd_segments(x, u, sizes, q, bucket, 0, codes, norms, dec)
 
 
+@pytest.mark.parametrize("sizes", [(1,), (129,), (64, 1, 129)], ids=lambda s: "n%d" % sum(s))
+def test_qsgd_cuda_variant_other_bucket(sizes):
+    """Variant 1 away from bucket 128 (bucket 100, 64 levels): qsgd_encode_kernel<int8, 1> on a
+    generic bucket and qsgd_decode_kernel<int8, 1, B128 = false>, the one arm of the launchers'
+    (code type, variant) choice that no other test reaches.  Codes, norms and the dense result are
+    written in front of a canary that has to survive."""
+    from grace_amd import _lib
+    q, bucket, guard = 64, 100, 64
+    n = sum(sizes)
+    rng = np.random.default_rng(6400 + n)
+    x = (rng.standard_normal(n) * 0.01).astype(F32)
+    u = rng.random(n, dtype=F32)
+    if n > 100:
+        x[[3, n - 2]] = [np.nan, -np.inf]     # the first and the last bucket hold a codeword -128
+    nb = sum(-(-s // bucket) for s in sizes)
+    cbuf = torch.full((n + guard,), 0x5A, dtype=torch.int8, device=DEV)
+    nbuf = torch.full((nb + guard,), -7.0, dtype=torch.float32, device=DEV)
+    dbuf = torch.full((n + guard,), -7.0, dtype=torch.float32, device=DEV)
+    codes, norms = ops.qsgd_compress(_t(x), q, bucket, sizes=list(sizes), variant=1, u=_t(u),
+                                     codes_out=cbuf[:n], norms_out=nbuf[:nb])
+    seg_off, bkt_off, nb_t = ops.seg_tables(list(sizes), bucket, codes.device)
+    assert nb_t == nb
+    dec = dbuf[:n]
+    _lib.call("grace_qsgd_decompress", ops._p(codes), ops._p(norms), n, nb, 1, ops._p(seg_off), ops._p(bkt_off),
+              len(sizes), n, q, bucket, 1, 0, 1.0, ops._p(dec), ops._stream())
+    check_qsgd_segments(x, u, sizes, q, bucket, 1, codes, norms, dec)
+    assert bool((cbuf[n:] == 0x5A).all()) and bool((nbuf[nb:] == -7.0).all()) and bool((dbuf[n:] == -7.0).all())
+    if n > 100:
+        assert (_np(codes) == -128).sum() == 2 and np.isnan(_np(dec)).sum() == 2
+
+
 @pytest.mark.parametrize("q", [127, 255])
 @pytest.mark.parametrize("odd", [False, True])
 @pytest.mark.parametrize("nseg", [512, 513, 700])

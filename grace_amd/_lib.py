@@ -1,6 +1,6 @@
 """ctypes binding of libgrace_hip.so (the C ABI declared in include/grace_hip.h,
-include/grace_hip_sign.h, include/grace_hip_quant.h, include/grace_hip_dgc.h and
-include/grace_hip_sparse.h).
+include/grace_hip_sign.h, include/grace_hip_quant.h, include/grace_hip_dgc.h,
+include/grace_hip_sparse.h and include/grace_hip_cast.h).
 
 The headers are the declaration: the binding tables below are parsed from their prototypes at
 import.  A new entry point is declared in its header and defined in the .hip that includes that
@@ -105,6 +105,8 @@ SIGNATURES_QUANT = _header_table("grace_hip_quant.h")
 SIGNATURES_DGC = _header_table("grace_hip_dgc.h")
 # threshold and random-k on bfloat16; the padded decode with a bf16 dense result
 SIGNATURES_SPARSE = _header_table("grace_hip_sparse.h")
+# natural, cnat, fp16 and one-bit on bfloat16; one-bit's fused step and W-rank decode
+SIGNATURES_CAST = _header_table("grace_hip_cast.h")
 
 _lock = threading.Lock()
 _lib = None
@@ -113,10 +115,10 @@ _fns = {}
 
 
 def _bind(lib, strict):
-    """Give every symbol of the five tables its restype and argtypes and return `lib`.  strict: a
+    """Give every symbol of the six tables its restype and argtypes and return `lib`.  strict: a
     symbol the library lacks raises AttributeError; otherwise it stays unbound."""
     for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items(), *SIGNATURES_QUANT.items(),
-                              *SIGNATURES_DGC.items(), *SIGNATURES_SPARSE.items()):
+                              *SIGNATURES_DGC.items(), *SIGNATURES_SPARSE.items(), *SIGNATURES_CAST.items()):
         f = getattr(lib, name) if strict else getattr(lib, name, None)
         if f is not None:
             f.restype = res

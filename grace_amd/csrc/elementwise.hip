@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "codec.h"
 
 namespace grace {
 
@@ -227,10 +228,7 @@ __global__ __launch_bounds__(kSignBlock) void sign_step_w1_kernel(const float* _
 // one-bit decode: mask0 * mean0 + notmask * mean1 (two products, then the add)
 struct OneBitDecOp {
   const uint8_t* m; const float* mean0; const float* mean1; int quirk; float* o;
-  __device__ float dec(uint32_t b, float m0, float m1) const {
-    float nb = quirk ? (float)(255u - b) : (float)(1u - b);
-    return (float)b * m0 + nb * m1;
-  }
+  __device__ float dec(uint32_t b, float m0, float m1) const { return onebit_dec(b, m0, m1, quirk); }
   __device__ void vec(int64_t i) const {
     const float m0 = mean0[0], m1 = mean1[0];
     uint32_t w = reinterpret_cast<const uint32_t*>(m)[i];
@@ -315,12 +313,7 @@ struct OneBitAcc {
 struct OneBitFin {
   static constexpr int K = 3;
   int64_t n; float* out;
-  __device__ void finish(const double* t) const {
-    const float sum0 = (float)t[0], num0 = (float)t[1], sum1 = (float)t[2];
-    const float num1 = (float)n - num0;
-    out[0] = num0 > 0.f ? sum0 / num0 : sum0;
-    out[1] = num1 > 0.f ? sum1 / num1 : sum1;
-  }
+  __device__ void finish(const double* t) const { onebit_means(t[0], t[1], t[2], n, out); }
 };
 
 template <typename Acc, typename Fin>

@@ -13,6 +13,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "codec.h"
 #include "../../include/grace_hip_quant.h"
 
 namespace grace {
@@ -1727,30 +1728,7 @@ __global__ __launch_bounds__(kQBlock) void tern_decode_records_kernel(const uint
 // accesses inside the same quad.
 __device__ __forceinline__ bool quad_fast(int64_t e, int64_t n, bool aligned) { return aligned && e + 3 < n; }
 
-// natural compression, cupy flavour (grace_dl/dist/compressor/natural.py:12-40): exponent
-// rounded up when mantissa > randint(0, 2^23 - 1), clipped to [18, 145], code = sign | (E - 18).
-__device__ __forceinline__ uint32_t natural_code(float xv, int32_t r) {
-  const int32_t bits = __float_as_int(xv);
-  const int32_t sign = bits & (int32_t)0x80000000;
-  int32_t e = bits & 0x7F800000;
-  const int32_t mant = bits & 0x007FFFFF;
-  if (mant > r) e += 0x00800000;
-  e = min(max(e, (int32_t)0x09000000), (int32_t)0x48800000);
-  return (uint32_t)(uint8_t)((sign >> 24) | ((e >> 23) - 18));
-}
-
-// device generator of the natural codec: one rand32 hash per quad plus xorshift32 steps
-// (uniform01x4's stream), mapped onto [0, 0x7FFFFF) by a high multiply (the reference's randint
-// range; the per-element 64-bit mixes and 64-bit modulo this replaced made the encoder ALU-bound)
-__device__ __forceinline__ void natural_rand4(uint64_t seed, int64_t e, int32_t (&r)[4]) {
-  uint32_t hq = rand32(seed, (uint64_t)e);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (j) { hq = hq ? hq : 0x9E3779B9u; hq ^= hq << 13; hq ^= hq >> 17; hq ^= hq << 5; }
-    r[j] = (int32_t)__umulhi(hq, 0x7FFFFFu);
-  }
-}
-
+// natural compression, cupy flavour: natural_code / natural_rand4 / natural_dec of codec.h
 __global__ __launch_bounds__(kQBlock) void natural_encode_kernel(const float* __restrict__ x, int64_t n,
                                                                 const int32_t* __restrict__ ri, uint64_t seed,
                                                                 uint8_t* __restrict__ codes, int aligned,
@@ -1786,26 +1764,7 @@ __global__ __launch_bounds__(kQBlock) void natural_encode_kernel(const float* __
   }
 }
 
-__device__ __forceinline__ float natural_dec(uint32_t c) {
-  const uint32_t e = c & 0x7F;
-  const float mag = __uint_as_float((e + 18u) << 23);
-  const float v = c > 127 ? -mag : mag;
-  return v * (e >= 1 ? 1.0f : 0.0f);   // 0x80 decodes to -0.0 as in the reference
-}
-
-// cnat_cuda flavour (cnat_cuda.cu:68-134): frexp mantissa m in [0.5, 1); exponent kept w.p.
-// 2|m| - 1; LUT: biased E <= 17 -> 0, E -> E - 17 saturating at 127, +128 if negative.
-__device__ __forceinline__ uint32_t cnat_code(float v, float r) {
-  if (v == 0.f) return 0u;
-  int ex;
-  const float prob = fabsf(frexpf(v, &ex)) / 0.5f - 1.0f;
-  if (r >= prob) ex -= 1;
-  const int biased = ex + 127;
-  int code = biased <= 17 ? 0 : min(biased - 17, 127);
-  if (v < 0.f) code += 128;
-  return (uint32_t)code;
-}
-
+// cnat_cuda flavour: cnat_code / cnat_dec of codec.h
 __global__ __launch_bounds__(kQBlock) void cnat_encode_kernel(const float* __restrict__ x, int64_t n,
                                                              const float* __restrict__ rnd, int deterministic,
                                                              uint64_t seed, uint8_t* __restrict__ codes,
@@ -1835,12 +1794,6 @@ __global__ __launch_bounds__(kQBlock) void cnat_encode_kernel(const float* __res
         if (e + j < n) codes[e + j] = (uint8_t)c[j];
     }
   }
-}
-
-__device__ __forceinline__ float cnat_dec(uint32_t c) {
-  const uint32_t m = c & 0x7F;
-  const uint32_t e = m == 0 ? 0u : m + 17u;
-  return __uint_as_float(((c >> 7) << 31) | (e << 23));
 }
 
 // decode (+ rank-ordered aggregate of W payloads at `stride`): 4 codes per 4-B load per rank,
@@ -1949,14 +1902,7 @@ __global__ __launch_bounds__(kQBlock) void f16_to_f32_kernel(const __half* __res
 // World-1 Allgather(Natural | Natural_CUDA | FP16, NoneMemory).step in ONE pass: out = 0 + dec(enc(x))
 // (the division by world size 1 is exact and omitted), with the same codes as the separate encode
 // kernels on the device generator -- the codes never reach memory (8 B per element instead of 10 / 12).
-enum CastMode : int { kCastNatural = 0, kCastCnat = 1, kCastCnatDet = 2, kCastF16 = 3 };
-template <int MODE>
-__device__ __forceinline__ float cast_round_trip(float v, float u, int32_t ri) {
-  if constexpr (MODE == kCastNatural) return 0.f + natural_dec(natural_code(v, ri));
-  else if constexpr (MODE == kCastCnat || MODE == kCastCnatDet) return 0.f + cnat_dec(cnat_code(v, u));
-  else return 0.f + __half2float(__float2half_rn(v));
-}
-
+// (CastMode and cast_round_trip: codec.h)
 template <int MODE>
 __global__ __launch_bounds__(kQBlock) void cast_step_w1_kernel(const float* __restrict__ x, float* __restrict__ o,
                                                               int64_t n, uint64_t seed) {

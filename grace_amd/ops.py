@@ -449,6 +449,62 @@ def onebit_encode(x):
     return mask0, means
 
 
+def onebit_encode_grad(x):
+    """onebit_encode on a gradient that is f32 or bf16 (the same payload for g and g.float()): (mask0
+    u8[n], means f32[2]).  Its own name, as axpby_grad beside axpby: onebit_encode is all the dtype
+    check grace_amd.dist's OneBitCompressor.compress has, and that class keeps refusing bf16."""
+    x = dev_grad(x, "tensor")
+    if x.dtype == F32:
+        return onebit_encode(x)
+    if x.numel() == 0:
+        raise ValueError("grace_amd: onebit_encode_grad: an empty tensor has no means")
+    mask0 = torch.empty(x.numel(), dtype=torch.uint8, device=x.device)
+    means = torch.empty(2, dtype=F32, device=x.device)
+    ws = workspace("reduce", _lib.query("grace_reduce_workspace_bytes", x.numel()), x.device)
+    _lib.call("grace_onebit_encode_bf16", _p(x), x.numel(), _p(mask0), _p(means), _p(ws), _stream())
+    return mask0, means
+
+
+def onebit_step_w1(x, quirk=False):
+    """World-1 Allgather(OneBit, NoneMemory).step in two launches (grace_onebit_step_w1, DESIGN.md
+    section 14): (means f32[2], 0 + decode of x's own payload in x's dtype and shape); x is f32 or
+    bf16.  The means are the ones the device used for the result."""
+    flat = dev_grad(x, "tensor")
+    n = flat.numel()
+    if n == 0:
+        raise ValueError("grace_amd: onebit_step_w1: an empty tensor has no means")
+    means = torch.empty(2, dtype=F32, device=flat.device)
+    out = torch.empty(x.shape, dtype=flat.dtype, device=flat.device)
+    ws = workspace("reduce", _lib.query("grace_reduce_workspace_bytes", n), flat.device)
+    _lib.call(_entry("grace_onebit_step_w1", flat.dtype), _p(flat), n, 1 if quirk else 0, _p(means), _p(out), _p(ws),
+              _stream())
+    return means, out
+
+
+def onebit_decode_aggregate(mask0, mean0, mean1, world, n, quirk=False, divisor=1.0, out_dtype=F32):
+    """(((0 + d_0) + d_1) + ...) / divisor over `world` gathered one-bit payloads (mask0
+    u8[world * n] rank-major, mean0 and mean1 f32[world]), in out_dtype: one launch, one rounding;
+    no division when divisor == 1."""
+    out_dtype = _dense_dtype(out_dtype, "onebit_decode_aggregate")
+    world, n = int(world), int(n)
+    if world < 1 or n < 0 or float(divisor) == 0.0:
+        raise ValueError("grace_amd: onebit_decode_aggregate: world must be at least 1, n at least 0 and divisor "
+                         "non-zero")
+    for t, dtype, count, what in ((mask0, torch.uint8, world * n, "mask0"), (mean0, F32, world, "mean0"),
+                                  (mean1, F32, world, "mean1")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != count or not t.is_contiguous():
+            raise TypeError(f"grace_amd: onebit_decode_aggregate: {what} must be a contiguous {dtype} tensor of "
+                            f"{count} elements")
+    mask0, mean0, mean1 = require_dev(mask0, "mask0"), require_dev(mean0, "mean0"), require_dev(mean1, "mean1")
+    if mean0.device != mask0.device or mean1.device != mask0.device:
+        raise ValueError("grace_amd: onebit_decode_aggregate: mask0 and the means must be on one device")
+    out = torch.empty(n, dtype=out_dtype, device=mask0.device)
+    if n:
+        _lib.call(_entry("grace_onebit_decode_aggregate", out_dtype), _p(mask0), _p(mean0), _p(mean1), world,
+                  1 if quirk else 0, float(divisor), _p(out), n, _stream())
+    return out
+
+
 def onebit_decode(mask0, mean0, mean1, quirk=False):
     mask0 = require_dev(mask0, "mask0")
     out = torch.empty(mask0.numel(), dtype=F32, device=mask0.device)
@@ -1141,36 +1197,64 @@ def terngrad_decompress(codes, scalars, n, sizes=None, world=1, aggregate=False,
 
 
 # ----------------------------------------------------------------------------- natural / fp16
+def _bf16_randoms(r, dtype, x, xoff, what):
+    """The checks of a bf16 encoder's injected randoms (None: the device generator) and of xoff."""
+    if int(xoff) < 0 or int(xoff) % 4:
+        raise ValueError(f"grace_amd: {what}: xoff must be a non-negative multiple of 4, got {xoff}")
+    if r is None:
+        return
+    if not isinstance(r, torch.Tensor) or r.dtype != dtype or not r.is_contiguous() or r.numel() < x.numel():
+        raise TypeError(f"grace_amd: {what} must be a contiguous {dtype} tensor of at least {x.numel()} elements")
+    if r.device != x.device:
+        raise ValueError(f"grace_amd: {what} must be on {x.device}, got {r.device}")
+
+
 def natural_compress(x, rand_int=None, seed=0, xoff=0, out=None):
     """xoff (a multiple of 4): the element of a larger bucket x[0] is, for the device generator."""
-    x = dev_f32(x)
+    x = dev_grad(x, "tensor")
+    if x.dtype == BF16:
+        _bf16_randoms(rand_int, torch.int32, x, xoff, "natural_compress: rand_int")
     codes = _out_buf(out, x.numel(), torch.uint8, x.device, "natural_compress")
-    _lib.call("grace_natural_compress_at", _p(x), int(xoff), x.numel(), _p(rand_int), seed64(seed),
+    _lib.call(_entry("grace_natural_compress_at", x.dtype), _p(x), int(xoff), x.numel(), _p(rand_int), seed64(seed),
               _p(codes), _stream())
     return codes
 
 
 def cnat_compress(x, rand=None, deterministic=False, seed=0, xoff=0, out=None):
     """xoff (a multiple of 4): the element of a larger bucket x[0] is, for the device generator."""
-    x = dev_f32(x)
+    x = dev_grad(x, "tensor")
+    if x.dtype == BF16:
+        _bf16_randoms(rand, F32, x, xoff, "cnat_compress: rand")
     codes = _out_buf(out, x.numel(), torch.uint8, x.device, "cnat_compress")
-    _lib.call("grace_cnat_compress_at", _p(x), int(xoff), x.numel(), _p(rand), 1 if deterministic else 0,
-              seed64(seed), _p(codes), _stream())
+    _lib.call(_entry("grace_cnat_compress_at", x.dtype), _p(x), int(xoff), x.numel(), _p(rand),
+              1 if deterministic else 0, seed64(seed), _p(codes), _stream())
     return codes
 
 
-def natural_decompress(codes, n, flavour, world=1, aggregate=False, divisor=1.0):
+def _bf16_payload(t, dtype, count, what):
+    """The checks of a gathered payload a bf16 decode reads: a contiguous device tensor of `count`."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != count or not t.is_contiguous():
+        raise TypeError(f"grace_amd: {what} must be a contiguous {dtype} tensor of {count} elements")
+    return require_dev(t, what)
+
+
+def natural_decompress(codes, n, flavour, world=1, aggregate=False, divisor=1.0, out_dtype=F32):
+    """out_dtype bfloat16: the rank-ordered sum and the division in f32, rounded once."""
+    if _dense_dtype(out_dtype, "natural_decompress") == BF16:
+        if int(world) < 1 or int(n) < 0 or int(flavour) not in (0, 1) or float(divisor) == 0.0:
+            raise ValueError("grace_amd: natural_decompress: world >= 1, n >= 0, flavour 0 or 1 and a non-zero divisor")
+        codes = _bf16_payload(codes, torch.uint8, int(world) * int(n), "natural_decompress: codes")
     codes = require_dev(codes)
-    out = torch.empty(n, dtype=F32, device=codes.device)
-    _lib.call("grace_natural_decompress", _p(codes), n, int(world), n, int(flavour), 1 if aggregate else 0,
-              float(divisor), _p(out), _stream())
+    out = torch.empty(n, dtype=out_dtype, device=codes.device)
+    _lib.call(_entry("grace_natural_decompress", out_dtype), _p(codes), n, int(world), n, int(flavour),
+              1 if aggregate else 0, float(divisor), _p(out), _stream())
     return out
 
 
 def fp16_compress(x, out=None):
-    x = dev_f32(x)
+    x = dev_grad(x, "tensor")
     h = _out_buf(out, x.numel(), torch.float16, x.device, "fp16_compress")
-    _lib.call("grace_fp16_compress", _p(x), _p(h), x.numel(), _stream())
+    _lib.call(_entry("grace_fp16_compress", x.dtype), _p(x), _p(h), x.numel(), _stream())
     return h
 
 
@@ -1204,19 +1288,32 @@ def w1_elementwise_ok(communicator, tensor):
 
 def cast_step_w1(x, mode, seed):
     """grace_cast_step_w1: out = 0 + decompress(compress(x)) for natural (0), cnat (1), cnat
-    deterministic (2) or fp16 (3), in one pass; same shape as x."""
+    deterministic (2) or fp16 (3), in one pass; same shape as x.  A bfloat16 x gives a new contiguous
+    bfloat16 result: the f32 result for x.float() rounded once."""
+    if isinstance(x, torch.Tensor) and x.dtype == BF16:
+        flat = dev_grad(x, "tensor")
+        if int(mode) not in (0, 1, 2, 3):
+            raise ValueError(f"grace_amd: cast_step_w1: mode must be 0, 1, 2 or 3, got {mode}")
+        out = torch.empty(x.shape, dtype=BF16, device=flat.device)
+        _lib.call(_entry("grace_cast_step_w1", BF16), _p(flat), flat.numel(), int(mode), seed64(seed), _p(out), _stream())
+        return out
     out = torch.empty_like(x)
     _lib.call("grace_cast_step_w1", _p(x), x.numel(), int(mode), seed64(seed), _p(out), _stream())
     return out
 
 
-def fp16_decompress_aggregate(h_all, n, world, divisor=1.0):
+def fp16_decompress_aggregate(h_all, n, world, divisor=1.0, out_dtype=F32):
     """Allgather-step decode of `world` rank-major f16 payloads of n elements each:
-    ((0 + d_0) + ... + d_{W-1}) / divisor in one pass (no division when divisor == 1)."""
+    ((0 + d_0) + ... + d_{W-1}) / divisor in one pass (no division when divisor == 1), in out_dtype
+    (bfloat16: rounded once after the division)."""
+    if _dense_dtype(out_dtype, "fp16_decompress_aggregate") == BF16:
+        if int(world) < 1 or int(n) < 0 or float(divisor) == 0.0:
+            raise ValueError("grace_amd: fp16_decompress_aggregate: world >= 1, n >= 0 and a non-zero divisor")
+        h_all = _bf16_payload(h_all, torch.float16, int(world) * int(n), "fp16_decompress_aggregate: h_all")
     h_all = require_dev(h_all)
-    out = torch.empty(n, dtype=F32, device=h_all.device)
-    _lib.call("grace_fp16_decompress_aggregate", _p(h_all), int(n), int(world), int(n), float(divisor), _p(out),
-              _stream())
+    out = torch.empty(n, dtype=out_dtype, device=h_all.device)
+    _lib.call(_entry("grace_fp16_decompress_aggregate", out_dtype), _p(h_all), int(n), int(world), int(n),
+              float(divisor), _p(out), _stream())
     return out
 
 

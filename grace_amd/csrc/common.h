@@ -17,6 +17,10 @@ namespace grace {
 
 constexpr int kWave = 64;
 
+// Workgroups (= partials) at most of the reductions that share grace_reduce_workspace_bytes(n):
+// that workspace is sizeof(double) * 4 * kRedBlocks bytes (elementwise.hip).
+constexpr int kRedBlocks = 1024;
+
 // aux operand of the raw buffer load / store builtins for the sc1 cache policy: 16-B write-through
 // stores (one fabric write per 16 B instead of one per dword) and loads that bypass the
 // (non-coherent) local L2 -- the agent-scope hand-offs of DESIGN.md §4
@@ -153,6 +157,20 @@ __device__ __forceinline__ double row16_sum(double v) {
   v += dpp_f64<0x141>(v);   // row_half_mirror
   v += dpp_f64<0x140>(v);   // row_mirror
   return v;
+}
+
+// Maximum of a 32-bit key over each 16-lane DPP row, by the same four butterflies: all 16 lanes
+// hold the row's maximum.
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_u32(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, false);
+}
+__device__ __forceinline__ uint32_t row16_max(uint32_t m) {
+  m = max(m, dpp_u32<0xB1>(m));    // quad_perm [1,0,3,2]
+  m = max(m, dpp_u32<0x4E>(m));    // quad_perm [2,3,0,1]
+  m = max(m, dpp_u32<0x141>(m));   // row_half_mirror
+  m = max(m, dpp_u32<0x140>(m));   // row_mirror
+  return m;
 }
 
 // Wave-level reductions (64 lanes) via cross-lane shuffles.

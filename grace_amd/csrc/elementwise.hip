@@ -241,7 +241,7 @@ struct OneBitDecOp {
 // ------------------------------------------------------------------------------------------------
 // Reductions: block partials in f64 (deterministic order per block), then one finishing block
 // that sums the partials in block order.  Used off the headline path (EF-sign mean, one-bit).
-constexpr int kRedBlocks = 1024;
+// kRedBlocks (common.h) caps the grid.
 
 template <int K>
 struct Partials { double v[K]; };

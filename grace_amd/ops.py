@@ -513,6 +513,138 @@ def onebit_decode(mask0, mean0, mean1, quirk=False):
     return out
 
 
+# ----------------------------------------------------------------------------- 8-bit codebook
+U8BIT_BLOCKS = (0, 256, 512, 1024, 2048, 4096)   # 0: one scale for the whole tensor
+U8BIT_LEVELS = 128
+_u8bit_dev = {}
+
+
+def u8bit_host_tables(rounding="floor", values=None):
+    """(edges, values) as CPU f32 tensors of 128 entries, validated; raises ValueError.  values=None is
+    the dynamic-tree table: 0, then for e = 1..6 the 2^e values 10^(e-6) * (0.1 + 0.9 * (2t+1) / 2^(e+1)),
+    then 1 (f64, rounded to f32).  rounding "floor" decodes to the lower edge (edges = values);
+    "nearest" puts each edge midway between neighbouring values (f64, rounded to f32), edges[0] = 0."""
+    if rounding not in ("floor", "nearest"):
+        raise ValueError(f"grace_amd: u8bit: rounding must be 'floor' or 'nearest', got {rounding!r}")
+    if values is None:
+        v = [0.0] + [10.0 ** (e - 6) * (0.1 + 0.9 * (2 * t + 1) / (2 * 2 ** e))
+                     for e in range(1, 7) for t in range(2 ** e)] + [1.0]
+    else:
+        if isinstance(values, torch.Tensor):
+            if values.device.type != "cpu" or not values.dtype.is_floating_point:
+                raise ValueError("grace_amd: u8bit: a codebook tensor must be a floating-point CPU tensor")
+            values = values.reshape(-1).tolist()
+        try:
+            v = [float(t) for t in values]
+        except (TypeError, ValueError) as e:
+            raise ValueError("grace_amd: u8bit: the codebook must be a sequence of 128 floats") from e
+    v32 = torch.tensor(v, dtype=torch.float64).to(F32)
+    if (v32.numel() != U8BIT_LEVELS or not bool(torch.isfinite(v32).all()) or float(v32[0]) < 0.0
+            or not bool((v32[1:] > v32[:-1]).all())):
+        raise ValueError(f"grace_amd: u8bit: the codebook must be {U8BIT_LEVELS} ascending finite float32 values, "
+                         "the first at least 0")
+    if rounding == "floor":
+        return v32.clone(), v32
+    v64 = v32.double()
+    edges = torch.cat([torch.zeros(1, dtype=torch.float64), (v64[:-1] + v64[1:]) / 2]).to(F32)
+    return edges, v32
+
+
+def u8bit_tables(rounding="floor", values=None):
+    """u8bit_host_tables on the current device, cached per device and table.  A codebook that is not
+    already a tuple is validated first (ValueError) and keyed by its 128 float32 values."""
+    if values is not None and not isinstance(values, tuple):
+        values = tuple(u8bit_host_tables(rounding, values)[1].tolist())
+    key = (torch.cuda.current_device(), rounding, values)
+    tabs = _u8bit_dev.get(key)
+    if tabs is None:
+        dev = torch.device("cuda", key[0])
+        tabs = _u8bit_dev[key] = tuple(t.to(dev) for t in u8bit_host_tables(rounding, values))
+    return tabs
+
+
+def _u8bit_scales(n, block, device):
+    # every scale is written by the kernel; only an empty tensor's single tensor-wide scale is not
+    nblk = -(-n // block) if block else 1
+    return torch.empty(nblk, dtype=F32, device=device) if n else torch.zeros(nblk, dtype=F32, device=device)
+
+
+def _u8bit_block(block, what):
+    if isinstance(block, bool) or block not in U8BIT_BLOCKS:
+        raise ValueError(f"grace_amd: {what}: block must be one of {U8BIT_BLOCKS}, got {block!r}")
+    return int(block)
+
+
+def _u8bit_table(t, device, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != F32 or t.numel() != U8BIT_LEVELS or not t.is_contiguous():
+        raise TypeError(f"grace_amd: {what} must be a contiguous float32 tensor of {U8BIT_LEVELS} entries")
+    if t.device != device:
+        raise ValueError(f"grace_amd: {what} must be on {device} (ops.u8bit_tables)")
+    return t
+
+
+def _u8bit_ws(block, n, device):
+    # its own slot: the first word is an arrival counter that stays zero between calls
+    return None if block else workspace("u8bit", _lib.query("grace_reduce_workspace_bytes", n), device)
+
+
+def u8bit_compress(x, block, edges):
+    """(codes i8[n], scales f32[nblk]) of a f32 or bf16 gradient (the same payload for g and g.float());
+    nblk = ceil(n / block), or 1 when block == 0 (include/grace_hip_u8bit.h)."""
+    block = _u8bit_block(block, "u8bit_compress")
+    x = dev_grad(x, "tensor")
+    edges = _u8bit_table(edges, x.device, "u8bit_compress: edges")
+    n = x.numel()
+    codes = torch.empty(n, dtype=torch.int8, device=x.device)
+    scales = _u8bit_scales(n, block, x.device)
+    if n:
+        _lib.call(_entry("grace_u8bit_compress", x.dtype), _p(x), n, block, _p(edges), _p(scales), _p(codes),
+                  _p(_u8bit_ws(block, n, x.device)), _stream())
+    return codes, scales
+
+
+def u8bit_step_w1(x, block, edges, values):
+    """World-1 Allgather(U8bit, NoneMemory).step (grace_u8bit_step_w1): (scales
+    f32[nblk], 0 + decode of x's own codes in x's dtype and shape); the codes are never stored."""
+    block = _u8bit_block(block, "u8bit_step_w1")
+    flat = dev_grad(x, "tensor")
+    edges = _u8bit_table(edges, flat.device, "u8bit_step_w1: edges")
+    values = _u8bit_table(values, flat.device, "u8bit_step_w1: values")
+    n = flat.numel()
+    scales = _u8bit_scales(n, block, flat.device)
+    out = torch.empty(x.shape, dtype=flat.dtype, device=flat.device)
+    if n:
+        _lib.call(_entry("grace_u8bit_step_w1", flat.dtype), _p(flat), n, block, _p(edges), _p(values), _p(scales),
+                  _p(out), _p(_u8bit_ws(block, n, flat.device)), _stream())
+    return scales, out
+
+
+def u8bit_decode_aggregate(codes, scales, world, n, block, values, divisor=1.0, out_dtype=F32):
+    """(((0 + d_0) + d_1) + ...) / divisor over `world` gathered payloads (codes i8[world * n] and scales
+    f32[world * nblk], rank-major), in out_dtype: one launch, one rounding; no division when
+    divisor == 1."""
+    out_dtype = _dense_dtype(out_dtype, "u8bit_decode_aggregate")
+    block = _u8bit_block(block, "u8bit_decode_aggregate")
+    world, n = int(world), int(n)
+    if world < 1 or world > 1024 or n < 0 or float(divisor) == 0.0:
+        raise ValueError("grace_amd: u8bit_decode_aggregate: world must be 1 to 1024, n at least 0 and divisor "
+                         "non-zero")
+    nblk = -(-n // block) if block else 1
+    for t, dtype, count, what in ((codes, torch.int8, world * n, "codes"), (scales, F32, world * nblk, "scales")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != count or not t.is_contiguous():
+            raise TypeError(f"grace_amd: u8bit_decode_aggregate: {what} must be a contiguous {dtype} tensor of "
+                            f"{count} elements")
+    codes, scales = require_dev(codes, "codes"), require_dev(scales, "scales")
+    if scales.device != codes.device:
+        raise ValueError("grace_amd: u8bit_decode_aggregate: codes and scales must be on one device")
+    values = _u8bit_table(values, codes.device, "u8bit_decode_aggregate: values")
+    out = torch.empty(n, dtype=out_dtype, device=codes.device)
+    if n:
+        _lib.call(_entry("grace_u8bit_decode_aggregate", out_dtype), _p(codes), n, _p(scales), world, n, block,
+                  _p(values), float(divisor), _p(out), _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- top-k
 TOPK_SMALL_N = 32768   # topk.hip kSmallN: buckets up to this size run in one workgroup (dense writes)
 

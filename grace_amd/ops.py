@@ -645,8 +645,103 @@ def u8bit_decode_aggregate(codes, scales, world, n, block, values, divisor=1.0, 
     return out
 
 
+# ----------------------------------------------------------------------------- quantile buckets
+SKETCH_MAX_Q = 256
+
+
+def _sketch_q(q, what):
+    if isinstance(q, bool) or not isinstance(q, int) or not 2 <= q <= SKETCH_MAX_Q:
+        raise ValueError(f"grace_amd: {what}: the number of buckets must be an int from 2 to {SKETCH_MAX_Q}, got {q!r}")
+    return q
+
+
+def _sketch_grad(x, what):
+    x = dev_grad(x, "tensor")
+    if x.numel() >= 2 ** 31:
+        raise ValueError(f"grace_amd: {what}: at most 2^31 - 1 elements, got {x.numel()}")
+    return x
+
+
+def _sketch_ws(n, q, device):
+    # its own slot; the codec zeroes what it uses on every call (include/grace_hip_sketch.h)
+    return workspace("sketch", _lib.query("grace_sketch_workspace_bytes", n, q), device)
+
+
+def sketch_code_bytes(n, q):
+    """Bytes of one rank's codes: n, or ceil(n / 2) when q <= 16 (two codes to a byte)."""
+    return n if q > 16 else (n + 1) // 2
+
+
+def sketch_edges(x, q):
+    """edges f32[q + 1] of a f32 or bf16 gradient: edges[j] = sorted(x)[floor(j * (n - 1) / q)], exact
+    (grace_sketch_edges).  An empty tensor has none: ValueError."""
+    q = _sketch_q(q, "sketch_edges")
+    x = _sketch_grad(x, "sketch_edges")
+    n = x.numel()
+    if n == 0:
+        raise ValueError("grace_amd: sketch_edges: an empty tensor has no order statistics")
+    edges = torch.empty(q + 1, dtype=F32, device=x.device)
+    _lib.call(_entry("grace_sketch_edges", x.dtype), _p(x), n, q, _p(edges), _p(_sketch_ws(n, q, x.device)), _stream())
+    return edges
+
+
+def sketch_compress(x, q, out=None):
+    """(codes u8[n], or u8[ceil(n / 2)] when q <= 16, and means f32[q]) of a f32 or bf16 gradient: the
+    same codes for g and g.float() (include/grace_hip_sketch.h).  out: the caller's buffer for the codes."""
+    q = _sketch_q(q, "sketch_compress")
+    x = _sketch_grad(x, "sketch_compress")
+    n = x.numel()
+    codes = _out_buf(out, sketch_code_bytes(n, q), torch.uint8, x.device, "grace_amd: sketch_compress")
+    means = torch.empty(q, dtype=F32, device=x.device) if n else torch.zeros(q, dtype=F32, device=x.device)
+    if n:
+        _lib.call(_entry("grace_sketch_compress", x.dtype), _p(x), n, q, _p(means), _p(codes),
+                  _p(_sketch_ws(n, q, x.device)), _stream())
+    return codes, means
+
+
+def sketch_step_w1(x, q):
+    """World-1 Allgather(Sketch, NoneMemory).step (grace_sketch_step_w1): (means f32[q], 0 + decode of
+    x's own codes in x's dtype and shape); the codes stay in the workspace."""
+    q = _sketch_q(q, "sketch_step_w1")
+    flat = _sketch_grad(x, "sketch_step_w1")
+    n = flat.numel()
+    means = torch.empty(q, dtype=F32, device=flat.device) if n else torch.zeros(q, dtype=F32, device=flat.device)
+    out = torch.empty(x.shape, dtype=flat.dtype, device=flat.device)
+    if n:
+        _lib.call(_entry("grace_sketch_step_w1", flat.dtype), _p(flat), n, q, _p(means), _p(out),
+                  _p(_sketch_ws(n, q, flat.device)), _stream())
+    return means, out
+
+
+def sketch_decode_aggregate(codes, means, world, n, q, divisor=1.0, out_dtype=F32, code_stride=None):
+    """(((0 + d_0) + d_1) + ...) / divisor over `world` gathered payloads (means f32[world * q]; rank w's
+    codes start at byte w * code_stride of `codes`, by default one row after another), in out_dtype:
+    one launch, one rounding; no division when divisor == 1."""
+    out_dtype = _dense_dtype(out_dtype, "sketch_decode_aggregate")
+    q = _sketch_q(q, "sketch_decode_aggregate")
+    world, n = int(world), int(n)
+    row = sketch_code_bytes(n, q)
+    stride = row if code_stride is None else int(code_stride)
+    if world < 1 or world > 1024 or n < 0 or n >= 2 ** 31 or float(divisor) == 0.0 or stride < row:
+        raise ValueError("grace_amd: sketch_decode_aggregate: world must be 1 to 1024, n from 0 to 2^31 - 1, divisor "
+                         "non-zero and code_stride at least a row of codes")
+    for t, dtype, count, what in ((codes, torch.uint8, (world - 1) * stride + row, "codes"),
+                                  (means, F32, world * q, "means")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != count or not t.is_contiguous():
+            raise TypeError(f"grace_amd: sketch_decode_aggregate: {what} must be a contiguous {dtype} tensor of "
+                            f"{count} elements")
+    codes, means = require_dev(codes, "codes"), require_dev(means, "means")
+    if means.device != codes.device:
+        raise ValueError("grace_amd: sketch_decode_aggregate: codes and means must be on one device")
+    out = torch.empty(n, dtype=out_dtype, device=codes.device)
+    if n:
+        _lib.call(_entry("grace_sketch_decode_aggregate", out_dtype), _p(codes), stride, _p(means), world, n, q,
+                  float(divisor), _p(out), _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- top-k
-TOPK_SMALL_N = 32768   # topk.hip kSmallN: buckets up to this size run in one workgroup (dense writes)
+TOPK_SMALL_N = 32768  # topk.hip kSmallN: buckets up to this size run in one workgroup (dense writes)
 
 
 def ratio_k(numel, ratio):

@@ -740,6 +740,88 @@ def sketch_decode_aggregate(codes, means, world, n, q, divisor=1.0, out_dtype=F3
     return out
 
 
+# ----------------------------------------------------------------------------- error-bounded variable width
+INCEPTIONN_MAX_BITS = 14
+
+
+def _inceptionn_b(b, what):
+    if isinstance(b, bool) or not isinstance(b, int) or not 1 <= b <= INCEPTIONN_MAX_BITS:
+        raise ValueError(f"grace_amd: {what}: the bound's bits must be an int from 1 to {INCEPTIONN_MAX_BITS}, got {b!r}")
+    return b
+
+
+def _inceptionn_grad(x, what):
+    x = dev_grad(x, "tensor")
+    if x.numel() >= 2 ** 31:
+        raise ValueError(f"grace_amd: {what}: at most 2^31 - 1 elements, got {x.numel()}")
+    return x
+
+
+def _inceptionn_header_bytes(n):
+    return 16 * ((-(-n // 4096) + 4) // 4)      # word 0 and a word a tile of 4096 elements, padded to 16 B
+
+
+def inceptionn_capacity_bytes(n):
+    """The worst-case payload of n elements (grace_inceptionn_capacity_bytes); 0 for n == 0."""
+    n = int(n)
+    if n < 0 or n >= 2 ** 31:
+        raise ValueError(f"grace_amd: inceptionn_capacity_bytes: n must be from 0 to 2^31 - 1, got {n}")
+    return int(_lib.query("grace_inceptionn_capacity_bytes", n))
+
+
+def inceptionn_compress(x, b):
+    """The payload of a f32 or bf16 gradient, the same for g and g.float(), in a uint8 buffer of the
+    worst-case size; inceptionn_payload_bytes(payload) of it are the wire (grace_inceptionn_compress)."""
+    b = _inceptionn_b(b, "inceptionn_compress")
+    x = _inceptionn_grad(x, "inceptionn_compress")
+    n = x.numel()
+    payload = torch.empty(inceptionn_capacity_bytes(n), dtype=torch.uint8, device=x.device)
+    if n:
+        _lib.call(_entry("grace_inceptionn_compress", x.dtype), _p(x), n, b, _p(payload), _stream())
+    return payload
+
+
+def inceptionn_payload_bytes(payload):
+    """The length of the wire inside a buffer inceptionn_compress returned: word 0, read on the host
+    (the one synchronisation of the codec)."""
+    return 16 * int(payload[:4].view(torch.int32).item()) if payload.numel() else 0
+
+
+def inceptionn_step_w1(x, b):
+    """World-1 Allgather(Inceptionn, NoneMemory).step (grace_inceptionn_step_w1): the decode of x's own
+    codes in x's dtype and shape, with no payload."""
+    b = _inceptionn_b(b, "inceptionn_step_w1")
+    flat = _inceptionn_grad(x, "inceptionn_step_w1")
+    out = torch.empty(x.shape, dtype=flat.dtype, device=flat.device)
+    if flat.numel():
+        _lib.call(_entry("grace_inceptionn_step_w1", flat.dtype), _p(flat), flat.numel(), b, _p(out), _stream())
+    return out
+
+
+def inceptionn_decode_aggregate(payloads, world, n, b, divisor=1.0, out_dtype=F32, stride=None):
+    """(((0 + d_0) + d_1) + ...) / divisor over `world` gathered payloads of n elements each (rank w's
+    starts at byte w * stride of `payloads`, by default numel / world), in out_dtype: one launch, one
+    rounding; no division when divisor == 1."""
+    out_dtype = _dense_dtype(out_dtype, "inceptionn_decode_aggregate")
+    b = _inceptionn_b(b, "inceptionn_decode_aggregate")
+    world, n = int(world), int(n)
+    if world < 1 or world > 1024 or n < 0 or n >= 2 ** 31 or float(divisor) == 0.0:
+        raise ValueError("grace_amd: inceptionn_decode_aggregate: world must be 1 to 1024, n from 0 to 2^31 - 1 and "
+                         "divisor non-zero")
+    if not isinstance(payloads, torch.Tensor) or payloads.dtype != torch.uint8 or not payloads.is_contiguous():
+        raise TypeError("grace_amd: inceptionn_decode_aggregate: payloads must be a contiguous uint8 tensor")
+    stride = payloads.numel() // world if stride is None else int(stride)
+    if stride % 16 or world * stride > payloads.numel() or (n and stride < _inceptionn_header_bytes(n)):
+        raise ValueError("grace_amd: inceptionn_decode_aggregate: stride must be a multiple of 16, at least the "
+                         "header, and world * stride at most the buffer")
+    payloads = require_dev(payloads, "payloads")
+    out = torch.empty(n, dtype=out_dtype, device=payloads.device)
+    if n:
+        _lib.call(_entry("grace_inceptionn_decode_aggregate", out_dtype), _p(payloads), stride, world, n, b,
+                  float(divisor), _p(out), _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- top-k
 TOPK_SMALL_N = 32768  # topk.hip kSmallN: buckets up to this size run in one workgroup (dense writes)
 

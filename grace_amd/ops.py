@@ -822,6 +822,100 @@ def inceptionn_decode_aggregate(payloads, world, n, b, divisor=1.0, out_dtype=F3
     return out
 
 
+# ----------------------------------------------------------------------------- adaptive quantisation
+ADAQ_CHUNK = 8192   # adaq.hip kAqChunk: elements a directory word and a workgroup cover
+
+
+def _adaq_ratio(ratio, what):
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 < ratio <= 1.0:
+        raise ValueError(f"grace_amd: {what}: the ratio must be a number in (0, 1], got {ratio!r}")
+    return float(ratio)
+
+
+def _adaq_grad(x, what):
+    x = dev_grad(x, "tensor")
+    if x.numel() >= 2 ** 31:
+        raise ValueError(f"grace_amd: {what}: at most 2^31 - 1 elements, got {x.numel()}")
+    return x
+
+
+def _adaq_n(n, what):
+    n = int(n)
+    if n < 0 or n >= 2 ** 31:
+        raise ValueError(f"grace_amd: {what}: n must be from 0 to 2^31 - 1, got {n}")
+    return n
+
+
+def _adaq_ws(n, device):
+    # its own slot; the codec zeroes what it counts in on every call (include/grace_hip_adaq.h)
+    return workspace("adaq", _lib.query("grace_adaq_workspace_bytes", n), device)
+
+
+def adaq_capacity(n, ratio):
+    """cap = ceil(n * ratio) + 4, the entries a payload has room for; 0 for n == 0.  The header's formula
+    on the host (one f64 product, one ceil): what grace_adaq_capacity returns."""
+    ratio = _adaq_ratio(ratio, "adaq_capacity")
+    n = _adaq_n(n, "adaq_capacity")
+    return math.ceil(float(n) * ratio) + 4 if n else 0
+
+
+def adaq_payload_bytes(n, ratio):
+    """The wire of n elements at `ratio` in bytes, fixed by the two: the header, a directory word per
+    chunk of 8192 elements and two bytes per entry, each part padded to 16 bytes; 0 for n == 0
+    (what grace_adaq_payload_bytes returns)."""
+    cap = adaq_capacity(n, ratio)
+    return 16 + 16 * (-(-(-(-int(n) // ADAQ_CHUNK)) // 4)) + 16 * (-(-cap // 8)) if cap else 0
+
+
+def adaq_compress(x, ratio):
+    """The payload of a f32 or bf16 gradient, the same for g and g.float(): uint8[adaq_payload_bytes],
+    every byte written (grace_adaq_compress, include/grace_hip_adaq.h)."""
+    ratio = _adaq_ratio(ratio, "adaq_compress")
+    x = _adaq_grad(x, "adaq_compress")
+    n = x.numel()
+    payload = torch.empty(adaq_payload_bytes(n, ratio), dtype=torch.uint8, device=x.device)
+    if n:
+        ws = _adaq_ws(n, x.device)
+        _lib.call(_entry("grace_adaq_compress", x.dtype), _p(x), n, ratio, _p(payload), _p(ws), ws.numel(), _stream())
+    return payload
+
+
+def adaq_step_w1(x, ratio):
+    """World-1 Allgather(Adaq, NoneMemory).step (grace_adaq_step_w1): the decode of x's own selection in
+    x's dtype and shape; no entries are written."""
+    ratio = _adaq_ratio(ratio, "adaq_step_w1")
+    flat = _adaq_grad(x, "adaq_step_w1")
+    n = flat.numel()
+    out = torch.empty(x.shape, dtype=flat.dtype, device=flat.device)
+    if n:
+        ws = _adaq_ws(n, flat.device)
+        _lib.call(_entry("grace_adaq_step_w1", flat.dtype), _p(flat), n, ratio, _p(out), _p(ws), ws.numel(), _stream())
+    return out
+
+
+def adaq_decode_aggregate(payloads, world, n, ratio, divisor=1.0, out_dtype=F32, stride=None):
+    """(((0 + d_0) + d_1) + ...) / divisor over `world` gathered payloads of n elements at `ratio` (rank w's
+    starts at byte w * stride of `payloads`, by default numel / world), in out_dtype: one launch, one
+    rounding; no division when divisor == 1."""
+    out_dtype = _dense_dtype(out_dtype, "adaq_decode_aggregate")
+    ratio = _adaq_ratio(ratio, "adaq_decode_aggregate")
+    world, n = int(world), _adaq_n(n, "adaq_decode_aggregate")
+    if world < 1 or world > 1024 or float(divisor) == 0.0:
+        raise ValueError("grace_amd: adaq_decode_aggregate: world must be 1 to 1024 and divisor non-zero")
+    if not isinstance(payloads, torch.Tensor) or payloads.dtype != torch.uint8 or not payloads.is_contiguous():
+        raise TypeError("grace_amd: adaq_decode_aggregate: payloads must be a contiguous uint8 tensor")
+    payloads = require_dev(payloads, "payloads")
+    stride = payloads.numel() // world if stride is None else int(stride)
+    if stride % 16 or world * stride > payloads.numel() or stride < adaq_payload_bytes(n, ratio):
+        raise ValueError("grace_amd: adaq_decode_aggregate: stride must be a multiple of 16, at least the payload, "
+                         "and world * stride at most the buffer")
+    out = torch.empty(n, dtype=out_dtype, device=payloads.device)
+    if n:
+        _lib.call(_entry("grace_adaq_decode_aggregate", out_dtype), _p(payloads), stride, world, n,
+                  adaq_capacity(n, ratio), float(divisor), _p(out), _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- top-k
 TOPK_SMALL_N = 32768  # topk.hip kSmallN: buckets up to this size run in one workgroup (dense writes)
 

@@ -1,7 +1,8 @@
 """ctypes binding of libgrace_hip.so (the C ABI declared in include/grace_hip.h,
 include/grace_hip_sign.h, include/grace_hip_quant.h, include/grace_hip_dgc.h,
 include/grace_hip_sparse.h, include/grace_hip_cast.h, include/grace_hip_u8bit.h,
-include/grace_hip_sketch.h, include/grace_hip_inceptionn.h and include/grace_hip_adaq.h).
+include/grace_hip_sketch.h, include/grace_hip_inceptionn.h, include/grace_hip_adaq.h and
+include/grace_hip_mx.h).
 
 The headers are the declaration: the binding tables below are parsed from their prototypes at
 import.  A new entry point is declared in its header and defined in the .hip that includes that
@@ -116,6 +117,8 @@ SIGNATURES_SKETCH = _header_table("grace_hip_sketch.h")
 SIGNATURES_INCEPTIONN = _header_table("grace_hip_inceptionn.h")
 # adaptive quantisation (exact per-sign top-k, 2-byte entries) on float32 and bfloat16
 SIGNATURES_ADAQ = _header_table("grace_hip_adaq.h")
+# the microscaling codec (block-scaled FP8, FP6 and FP4) on float32 and bfloat16
+SIGNATURES_MX = _header_table("grace_hip_mx.h")
 
 _lock = threading.Lock()
 _lib = None
@@ -124,12 +127,12 @@ _fns = {}
 
 
 def _bind(lib, strict):
-    """Give every symbol of the ten tables its restype and argtypes and return `lib`.  strict: a
+    """Give every symbol of the eleven tables its restype and argtypes and return `lib`.  strict: a
     symbol the library lacks raises AttributeError; otherwise it stays unbound."""
     for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SIGN.items(), *SIGNATURES_QUANT.items(),
                               *SIGNATURES_DGC.items(), *SIGNATURES_SPARSE.items(), *SIGNATURES_CAST.items(),
                               *SIGNATURES_U8BIT.items(), *SIGNATURES_SKETCH.items(),
-                              *SIGNATURES_INCEPTIONN.items(), *SIGNATURES_ADAQ.items()):
+                              *SIGNATURES_INCEPTIONN.items(), *SIGNATURES_ADAQ.items(), *SIGNATURES_MX.items()):
         f = getattr(lib, name) if strict else getattr(lib, name, None)
         if f is not None:
             f.restype = res

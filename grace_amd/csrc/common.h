@@ -172,6 +172,15 @@ __device__ __forceinline__ uint32_t row16_max(uint32_t m) {
   m = max(m, dpp_u32<0x140>(m));   // row_mirror
   return m;
 }
+// The same over each aligned group of 4 or 8 lanes: the first two or three of those butterflies.
+__device__ __forceinline__ uint32_t quad_max(uint32_t m) {
+  m = max(m, dpp_u32<0xB1>(m));
+  return max(m, dpp_u32<0x4E>(m));
+}
+__device__ __forceinline__ uint32_t row8_max(uint32_t m) {
+  m = quad_max(m);
+  return max(m, dpp_u32<0x141>(m));
+}
 
 // Wave-level reductions (64 lanes) via cross-lane shuffles.
 template <typename T>

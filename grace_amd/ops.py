@@ -916,6 +916,93 @@ def adaq_decode_aggregate(payloads, world, n, ratio, divisor=1.0, out_dtype=F32,
     return out
 
 
+# ----------------------------------------------------------------------------- microscaling (MX)
+MX_FORMATS = ("fp8_e4m3", "fp8_e5m2", "fp6_e2m3", "fp6_e3m2", "fp4_e2m1")   # the C ABI's format 0..4
+MX_BITS = (8, 8, 6, 6, 4)
+MX_ROUNDINGS = ("nearest", "stochastic")
+
+
+def _mx_format(fmt, what):
+    if not isinstance(fmt, str) or fmt not in MX_FORMATS:
+        raise ValueError(f"grace_amd: {what}: the format must be one of {MX_FORMATS}, got {fmt!r}")
+    return MX_FORMATS.index(fmt)
+
+
+def _mx_rounding(rounding, what):
+    if not isinstance(rounding, str) or rounding not in MX_ROUNDINGS:
+        raise ValueError(f"grace_amd: {what}: the rounding must be one of {MX_ROUNDINGS}, got {rounding!r}")
+    return MX_ROUNDINGS.index(rounding)
+
+
+def _mx_uniforms(u, x, what):
+    """The injected uniforms of a stochastic call: None, or a contiguous f32 tensor, one per element, on x's device."""
+    if u is None:
+        return None
+    if not isinstance(u, torch.Tensor) or u.dtype != F32 or not u.is_contiguous() or u.numel() != x.numel():
+        raise ValueError(f"grace_amd: {what}: u must be a contiguous float32 tensor of {x.numel()} elements")
+    if u.device != x.device:
+        raise GraceDeviceError(f"grace_amd: {what}: u must be on {x.device}, got {u.device}")
+    return u
+
+
+def mx_payload_bytes(n, fmt):
+    """The wire of n elements in bytes, fixed by (n, format): a scale byte per block of 32 and 4 * bits code
+    bytes per block, each part padded to 16 (what grace_mx_payload_bytes returns)."""
+    f = _mx_format(fmt, "mx_payload_bytes")
+    nb = -(-_adaq_n(n, "mx_payload_bytes") // 32)
+    return 16 * -(-nb // 16) + 16 * -(-nb * 4 * MX_BITS[f] // 16)
+
+
+def mx_compress(x, fmt="fp8_e4m3", rounding="nearest", seed=0, u=None):
+    """The payload of a f32 or bf16 gradient, the same for g and g.float(): uint8[mx_payload_bytes], every
+    byte written (grace_mx_compress, include/grace_hip_mx.h).  Stochastic rounding draws on the device from
+    `seed`, or reads the uniforms `u`."""
+    f, r = _mx_format(fmt, "mx_compress"), _mx_rounding(rounding, "mx_compress")
+    x = _adaq_grad(x, "mx_compress")
+    u = _mx_uniforms(u, x, "mx_compress")
+    n = x.numel()
+    payload = torch.empty(mx_payload_bytes(n, fmt), dtype=torch.uint8, device=x.device)
+    if n:
+        _lib.call(_entry("grace_mx_compress", x.dtype), _p(x), n, f, r, seed64(seed), _p(u), _p(payload), _stream())
+    return payload
+
+
+def mx_step_w1(x, fmt="fp8_e4m3", rounding="nearest", seed=0, u=None):
+    """World-1 Allgather(MX, NoneMemory).step (grace_mx_step_w1): decode(encode(x)) in x's dtype and shape;
+    neither codes nor scales are stored."""
+    f, r = _mx_format(fmt, "mx_step_w1"), _mx_rounding(rounding, "mx_step_w1")
+    flat = _adaq_grad(x, "mx_step_w1")
+    u = _mx_uniforms(u, flat, "mx_step_w1")
+    n = flat.numel()
+    out = torch.empty(x.shape, dtype=flat.dtype, device=flat.device)
+    if n:
+        _lib.call(_entry("grace_mx_step_w1", flat.dtype), _p(flat), n, f, r, seed64(seed), _p(u), _p(out), _stream())
+    return out
+
+
+def mx_decode_aggregate(payloads, world, n, fmt, divisor=1.0, out_dtype=F32, stride=None):
+    """((d_0 + d_1) + ...) / divisor over `world` gathered payloads of n elements (rank w's starts at byte
+    w * stride of `payloads`, by default numel / world), in out_dtype: one launch, one rounding; no division
+    when divisor == 1."""
+    out_dtype = _dense_dtype(out_dtype, "mx_decode_aggregate")
+    f = _mx_format(fmt, "mx_decode_aggregate")
+    world, n = int(world), _adaq_n(n, "mx_decode_aggregate")
+    if world < 1 or world > 1024 or float(divisor) == 0.0:
+        raise ValueError("grace_amd: mx_decode_aggregate: world must be 1 to 1024 and divisor non-zero")
+    if not isinstance(payloads, torch.Tensor) or payloads.dtype != torch.uint8 or not payloads.is_contiguous():
+        raise TypeError("grace_amd: mx_decode_aggregate: payloads must be a contiguous uint8 tensor")
+    payloads = require_dev(payloads, "payloads")
+    stride = payloads.numel() // world if stride is None else int(stride)
+    if stride % 16 or world * stride > payloads.numel() or stride < mx_payload_bytes(n, fmt):
+        raise ValueError("grace_amd: mx_decode_aggregate: stride must be a multiple of 16, at least the payload, "
+                         "and world * stride at most the buffer")
+    out = torch.empty(n, dtype=out_dtype, device=payloads.device)
+    if n:
+        _lib.call(_entry("grace_mx_decode_aggregate", out_dtype), _p(payloads), stride, world, n, f, float(divisor),
+                  _p(out), _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- top-k
 TOPK_SMALL_N = 32768  # topk.hip kSmallN: buckets up to this size run in one workgroup (dense writes)
 
